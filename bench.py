@@ -17,6 +17,11 @@ line carries `expected_speedup` with its basis: 64K instances are 1024 waves, on
 of ONE GPU, so splitting them over more GPUs leaves SIMDs idle without shortening any
 wave -- about 1x (C5's 4096 waves: up to 4x).
 
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs when
+--dump-outputs DIR is given, and prints the line. --full adds every other leg: the CPU
+baseline with its bit-exact check of the GPU results, the memory checksum (hash kernel), the
+fresh-input steps, the rooflines, and at N > 1 the weak-scaling phase.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -458,6 +463,33 @@ class Phase:
         self.ctx.close()
 
 
+DUMP_MAX_INSTANCES = 1 << 20   # x 4 float64 per instance = 32 MiB (5 with `index`: 40 MiB)
+
+
+def dump_outputs(path, dist, rets, st, cnt):
+    """--dump-outputs: what WasmEdge_BatchResults handed back after the last timed step, one
+    float64 .npy per array (every value below 2^53, so exact): `returns` [n, 2] = the low and
+    the high 32 bits of each instance's 64-bit return value (0 for a trapped instance, whose
+    return value is undefined), `status` [n] the per-instance ErrCode, `counts` [n] the
+    per-instance instruction count. 65,536 instances are 2 MiB in all (C5's 262,144: 8 MiB).
+    The inputs derive from the instance ids alone, so two runs with the same arguments hold
+    the same arrays. Past DUMP_MAX_INSTANCES (32 MiB; over all ranks) a fixed, seeded sample of that many
+    instances is written, with its instance numbers as `index`. With one process per GPU each
+    rank writes its shard as <name>.rank<r>."""
+    os.makedirs(path, exist_ok=True)
+    lo = np.where(st == 0, rets["lo"][:, 0], np.uint64(0)).astype(np.uint64)
+    arrays = {"returns": np.stack([lo & np.uint64(0xFFFFFFFF), lo >> np.uint64(32)], 1),
+              "status": st, "counts": cnt}
+    cap = DUMP_MAX_INSTANCES // dist.world
+    if len(st) > cap:
+        idx = np.sort(np.random.default_rng(0).choice(len(st), cap, replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, index=idx)
+    tag = ".rank%d" % dist.rank if dist.world > 1 else ""
+    for name, a in arrays.items():
+        assert int(a.max(initial=0)) < (1 << 53)
+        np.save(os.path.join(path, name + tag + ".npy"), a.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,10 +516,20 @@ def main():
     ap.add_argument("--elements", type=int, default=262144, help="C3 i32 per instance")
     ap.add_argument("--vary-args", default="auto", choices=["auto", "on", "off"],
                     help="also measure fresh inputs every step (the learned wave order and "
-                         "layout never see them); auto = on for c5 and mt")
+                         "layout never see them); auto = on for c5 and mt under --full")
     ap.add_argument("--cost-limit", type=int, default=0,
                     help="meter gas with the unit cost table up to this limit (measures the "
                          "cost of exact metering; not the headline configuration)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU baseline (and its "
+                         "bit-exact check of the GPU results), the memory checksum, the "
+                         "fresh-input steps (--vary-args auto), the rooflines, and at --gpus N > 1 "
+                         "the weak-scaling phase. A plain run sets up, warms up, times --steps "
+                         "steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned to its caller "
+                         "(WasmEdge_BatchResults: return values, status, instruction counts) as "
+                         "DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.workload == "c2" else 3
@@ -498,7 +540,7 @@ def main():
     if args.instances is None:
         args.instances = default_instances(args.workload)
     if args.vary_args == "auto":
-        args.vary_args = "on" if args.workload in ("c5", "mt") else "off"
+        args.vary_args = "on" if args.full and args.workload in ("c5", "mt") else "off"
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1 and not args.in_process:
@@ -522,10 +564,12 @@ def main():
     elapsed, ksum = ph.timed(args.steps)
     instrs_per_step, traps, ctx, n = ph.instrs_per_step, ph.traps, ph.ctx, ph.n
     total_instrs = dist.sum(instrs_per_step) * args.steps
+    rets, st, cnt = ctx.results(1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dist, rets, st, cnt)
     # checksum of checksums over every instance's final linear memory (hash kernel, after
     # the timed region; before the fresh-input steps, which leave other instances' states)
-    rets, st, cnt = ctx.results(1)
-    hashes = ctx.memory_hash()
+    hashes = ctx.memory_hash() if args.full else None
     fresh = None
     if args.vary_args == "on":
         fi, fs, fk = ph.fresh(args.steps)
@@ -537,7 +581,6 @@ def main():
                          "the arguments and is not reused; SetArgs before each step's clock, "
                          "the clock covers Reset + Run as for `value`"
                          % ("262144" if args.workload == "c5" else "2^30")}
-    checksum = int(hashes.sum(dtype=np.uint64))
     gpu = {"counts": cnt, "hashes": hashes, "status": st, "ret": rets["lo"][:, 0],
            "ret32": args.workload not in ("c5", "mt")}
     kernel_avg = ksum / args.steps
@@ -572,12 +615,13 @@ def main():
                         "parallelism": par,
                         "compiled_runs": ctx.compiled_runs(), "engine": ctx.engine(),
                         "granule": ctx.memory_granule()}, **extra),
-        "memory_checksum": "%016x" % checksum,
         "kernel_instr_per_s": total_instrs / (dist.max(kernel_avg) * args.steps),
         # the interpreter kernel's mean duration per step, HIP events on the library's stream
         # (the rooflines' time basis); ms_per_step adds the Reset and the launch gaps
         "kernel_ms": 1e3 * dist.max(kernel_avg),
     }
+    if args.full:
+        out["memory_checksum"] = "%016x" % int(hashes.sum(dtype=np.uint64))
     if fresh:
         out["fresh_input"] = fresh
     if args.workload == "c4":
@@ -586,7 +630,7 @@ def main():
         out["config"]["cost_limit"] = args.cost_limit
     c3_bytes_per_instr, c3_bpi_src = C3_BYTES_PER_INSTR, ", committed oracle figure"
     c3_split = None
-    if dist.rank == 0 and dist.world == 1 and not devices and not args.no_cpu_baseline:
+    if args.full and dist.rank == 0 and dist.world == 1 and not devices and not args.no_cpu_baseline:
         threads = host_cores()
         out["cpu_baseline"], bpi, c3_split = cpu_baseline(wasm, func, build_rows, ptypes, args.cpu_seconds,
                                                           threads, gpu, args.workload.upper(),
@@ -599,15 +643,16 @@ def main():
         out["data"] = "synthetic: per-instance inputs derived from the instance id"
     out["workload_key"] = args.workload
     out.update(e2e)
-    prof = load_profile(args.workload, out["config"])
-    kernel_max = dist.max(kernel_avg)
-    rooflines(out, args, prof, instrs_per_step, kernel_max, n, c3_bytes_per_instr, c3_bpi_src, c3_split)
+    if args.full:
+        prof = load_profile(args.workload, out["config"])
+        kernel_max = dist.max(kernel_avg)
+        rooflines(out, args, prof, instrs_per_step, kernel_max, n, c3_bytes_per_instr, c3_bpi_src, c3_split)
     ph.close()
     # the metric's configuration at N > 1 is the fixed total (strong); the weak-scaling
     # figure (every rank --instances of its own) rides along as an extra key
     if n_gpus > 1:
         out["expected_speedup"] = expected_speedup(out["config"]["instances"], n_gpus, args.scaling)
-    if n_gpus > 1 and args.scaling == "strong" and not args.no_weak:
+    if args.full and n_gpus > 1 and args.scaling == "strong" and not args.no_weak:
         wids = shard_ids(dist.rank, args.instances, dist.world, "weak") if not devices else \
             np.arange(args.instances * len(devices), dtype=np.int64)
         wp = Phase(args, dist, wids, devices)

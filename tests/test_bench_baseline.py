@@ -70,6 +70,69 @@ def test_vary_ids_are_fresh_permutations():
     assert (v != np.arange(65536)).all() and v.max() < (1 << 30)
 
 
+def test_dump_outputs_are_exact_float64(tmp_path, monkeypatch):
+    """--dump-outputs: return values as (low, high) 32-bit halves, status and counts, all
+    float64 and exact; a trapped instance's return value (undefined) is written as 0."""
+    import bench
+    from wasmedge_amd import batch
+    rets = np.zeros((4, 1), batch.VALUE_DTYPE)
+    rets["lo"][:, 0] = [7, (1 << 63) + 5, 0xDEADBEEF, 1 << 32]
+    st = np.array([0, 0, 0x88, 0], np.uint8)
+    cnt = np.array([1, 1 << 40, 3, 4], np.uint64)
+    bench.dump_outputs(str(tmp_path / "d"), types.SimpleNamespace(rank=0, world=1), rets, st, cnt)
+    got = {n: np.load(str(tmp_path / "d" / (n + ".npy"))) for n in ("returns", "status", "counts")}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["returns"].tolist() == [[7, 0], [5, 1 << 31], [0, 0], [0, 1]]
+    assert got["status"].tolist() == [0, 0, 0x88, 0] and got["counts"].tolist() == [1, 1 << 40, 3, 4]
+    # past the size cap: the same seeded sample of instances every time, with its index
+    monkeypatch.setattr(bench, "DUMP_MAX_INSTANCES", 2)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), types.SimpleNamespace(rank=0, world=1), rets, st, cnt)
+    idx = np.load(str(tmp_path / "s1" / "index.npy"))
+    assert idx.shape == (2,) and np.array_equal(idx, np.load(str(tmp_path / "s2" / "index.npy")))
+    assert np.array_equal(np.load(str(tmp_path / "s1" / "counts.npy")), got["counts"][idx.astype(int)])
+
+
+def _bench(*argv):
+    import json
+    import subprocess
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(argv),
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [json.loads(x) for x in out.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    return lines[0]
+
+
+@pytest.mark.gpu
+def test_gpu_bench_plain_run_is_lean_and_full_keeps_every_leg(built, tmp_path):
+    """A plain run times exactly --steps steps and prints the headline keys only; --full adds
+    the CPU baseline (bit-exact check), checksum and rooflines; --dump-outputs writes the
+    same arrays from run to run, equal to the oracle's for the same instances."""
+    import oracle_py
+    import bench
+    small = ["--gpus", "1", "--instances", "192", "--iters", "3", "--steps", "2", "--warmup", "1"]
+    a = _bench(*small, "--dump-outputs", str(tmp_path / "a"))
+    b = _bench(*small, "--full", "--cpu-seconds", "0.4", "--dump-outputs", str(tmp_path / "b"))
+    for line in (a, b):
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "instr/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "i32" and line["metric"] == bench.METRIC
+        assert abs(line["value"] - 192 * line["config"]["instrs_per_instance"] / (1e-3 * line["ms_per_step"])) \
+            <= 1e-9 * line["value"]
+    moved = ("cpu_baseline", "memory_checksum", "roofline", "hbm_roofline")
+    assert not any(k in a for k in moved) and all(k in b for k in moved)
+    got = {n: (np.load(str(tmp_path / "a" / (n + ".npy"))), np.load(str(tmp_path / "b" / (n + ".npy"))))
+           for n in ("returns", "status", "counts")}
+    for x, y in got.values():
+        assert x.dtype == np.float64 and x.shape[0] == 192 and np.array_equal(x, y)
+    wasm, func, build_rows, ptypes, _desc, _extra = bench.workload("c2", types.SimpleNamespace(iters=3))
+    m = oracle_py.Module(wasm)
+    for i, row in enumerate(build_rows(np.arange(192, dtype=np.int64)).tolist()):
+        code, ref, rcnt, _ = m.run(func, row)
+        assert (code, ref[0] & 0xFFFFFFFF, rcnt) == \
+            (got["status"][0][i], got["returns"][0][i, 0], got["counts"][0][i]), i   # (C2 returns an i32)
+
+
 def test_default_instances_are_the_metric_config():
     import bench
     assert bench.default_instances("c2") == 65536 and bench.default_instances("c3") == 65536

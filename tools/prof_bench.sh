@@ -14,7 +14,7 @@ OUT=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/$OUT
 cd /tmp && export TMPDIR=/tmp
-B="$R/bench.py --no-cpu-baseline $*"
+B="$R/bench.py --full --no-cpu-baseline $*"
 T=${PROF_TIMEOUT:-300}
 PASSES=${PROF_PASSES:-"trace fetch write sq1 sq2 util lat"}
 k=0
