@@ -314,6 +314,41 @@ WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchResults(WasmEdge_BatchContext *Cxt, WasmEdge_Value *Returns,
                       const uint32_t ReturnLen, uint8_t *PerInstance, uint64_t *InstrCounts);
 
+/* ---- per-instance calls ---------------------------------------------------------------
+ * Each instance runs its own export: N independent WasmEdge_VMExecute calls
+ * (wasmedge.h:3301) in one launch. FuncOf[i] indexes FuncNames, or is
+ * WASMEDGE_BATCH_NO_CALL. Params is [NumInstances][ParamStride] row-major; instance i
+ * passes the first ParamLens[i] values of its row (ParamLens NULL: ParamStride each).
+ *   - a name that is not an exported function: FuncNotFound (0x05) in PerInstance[i]
+ *     (lib/vm/vm.cpp:287-308);
+ *   - a ParamLens[i] or value types that do not match the function: FuncSigMismatch (0x83)
+ *     in PerInstance[i] (lib/executor/executor.cpp:88-100);
+ *   - NO_CALL: status 0.
+ * None of these three runs: instruction count 0, returns zeroed, its memory, globals,
+ * tables and gas total untouched; the other instances run normally. The call itself fails
+ * only on setup errors: a NULL context or a FuncOf[i] that is neither NO_CALL nor
+ * < NumFuncs (WrongVMWorkflow 0x04, the previous staging intact), an externref that cannot
+ * be interned, and -- at BatchRun -- a called export that is a host import.
+ * After SetCalls, BatchRun and BatchResults work as after SetArgs: Results' ReturnLen is the
+ * row stride, row i holds its function's results (their count: BatchGetReturnLens) with its
+ * result types, then zeroed values. A later BatchSetArgs returns to one function for all. */
+#define WASMEDGE_BATCH_NO_CALL 0xFFFFFFFFu
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSetCalls(WasmEdge_BatchContext *Cxt, const WasmEdge_String *FuncNames,
+                       const uint32_t NumFuncs, const uint32_t *FuncOf,
+                       const WasmEdge_Value *Params, const uint32_t ParamStride,
+                       const uint32_t *ParamLens);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchExecuteCalls(WasmEdge_BatchContext *Cxt, const WasmEdge_String *FuncNames,
+                           const uint32_t NumFuncs, const uint32_t *FuncOf,
+                           const WasmEdge_Value *Params, const uint32_t ParamStride,
+                           const uint32_t *ParamLens, WasmEdge_Value *Returns,
+                           const uint32_t ReturnStride, uint32_t *ReturnLens /* may be NULL */,
+                           uint8_t *PerInstance, uint64_t *InstrCounts);
+/* ReturnLens[i]: the result count of instance i's function (0 for one that did not run). */
+WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchGetReturnLens(WasmEdge_BatchContext *Cxt,
+                                                               uint32_t *ReturnLens);
+
 /* ---- host functions (the yield path) --------------------------------
  * A lane that calls an imported function parks on the device; BatchRun / BatchReset then
  * call the host function registered for that import on the CPU, once per parked lane,

@@ -30,6 +30,7 @@ STATUS_NAMES = {0x00: "ok", 0x07: "interrupted", 0x84: "integer divide by zero",
 
 
 ALL_INSTANCES = 0xFFFFFFFF
+NO_CALL = 0xFFFFFFFF    # WASMEDGE_BATCH_NO_CALL: the instance sits a set_calls run out
 REF_NULL = 0xFFFFFFFF   # null funcref / externref on the device (32-bit references)
 
 
@@ -147,6 +148,10 @@ def lib():
             ("WasmEdge_BatchResults", [vp, vp, u32, vp, vp]),
             ("WasmEdge_BatchMemoryHash", [vp, vp]),
             ("WasmEdge_BatchGetMemory", [vp, u32, u32, vp, u32]),
+            ("WasmEdge_BatchSetCalls", [vp, ctypes.POINTER(_String), u32, vp, vp, u32, vp]),
+            ("WasmEdge_BatchExecuteCalls", [vp, ctypes.POINTER(_String), u32, vp, vp, u32, vp,
+                                            vp, u32, vp, vp, vp]),
+            ("WasmEdge_BatchGetReturnLens", [vp, vp]),
         ]:
             f = getattr(L, name)
             f.restype = _Result
@@ -353,6 +358,62 @@ class BatchContext:
         self.set_args(func, values)
         self.run()
         return self.results(nret)
+
+    # per-instance calls (WasmEdge_BatchSetCalls / ExecuteCalls / GetReturnLens)
+    def set_calls(self, funcs, func_of, rows):
+        """Each instance its own export: funcs = the export names, func_of[i] = instance i's
+        index into funcs or None (no call: it sits the run out with status 0), rows[i] = its
+        arguments as (value, valtype) pairs (ints, bit patterns for floats). An unknown
+        name gives that instance 0x05, arguments that do not match its function 0x83; run()
+        and results(stride) then work as after set_args."""
+        keep, args = self._pack_calls(funcs, func_of, rows)
+        self._check(lib().WasmEdge_BatchSetCalls(self._h, *args))
+        self.func = None
+        self._keep = keep
+
+    def _pack_calls(self, funcs, func_of, rows):
+        if len(func_of) != self.n or len(rows) != self.n:
+            raise ValueError("func_of and rows must have %d entries" % self.n)
+        names = [f.encode() for f in funcs]
+        arr = (_String * max(len(names), 1))(*[_String(len(b), b) for b in names])
+        fo = np.array([NO_CALL if f is None else f for f in func_of], np.uint32)
+        lens = np.array([len(r) for r in rows], np.uint32)
+        stride = int(lens.max()) if self.n else 0
+        vals = np.zeros((self.n, max(stride, 1)), VALUE_DTYPE)
+        for i, r in enumerate(rows):
+            for k, (v, t) in enumerate(r):
+                v = int(v) & ((1 << 128) - 1)
+                vals["lo"][i, k] = v & 0xFFFFFFFFFFFFFFFF
+                vals["hi"][i, k] = v >> 64
+                vals["type"][i, k] = t
+        return (names, arr, fo, vals, lens), (arr, len(names), fo.ctypes.data,
+                                              vals.ctypes.data if stride else None, stride,
+                                              lens.ctypes.data)
+
+    def return_lens(self):
+        """Result count of each instance's function (0 where it did not run)."""
+        lens = np.zeros(self.n, np.uint32)
+        self._check(lib().WasmEdge_BatchGetReturnLens(self._h, lens.ctypes.data))
+        return lens
+
+    def execute_calls(self, funcs, func_of, rows, max_returns=8):
+        """WasmEdge_BatchExecuteCalls (arguments as set_calls): (rets, status, counts),
+        rets[i] = instance i's return values as python ints, as many as its function has
+        (up to max_returns; none unless its status is 0)."""
+        keep, args = self._pack_calls(funcs, func_of, rows)
+        rets = np.zeros((self.n, max(max_returns, 1)), VALUE_DTYPE)
+        lens = np.zeros(self.n, np.uint32)
+        status = np.zeros(self.n, np.uint8)
+        counts = np.zeros(self.n, np.uint64)
+        self._check(lib().WasmEdge_BatchExecuteCalls(self._h, *args, rets.ctypes.data, max_returns,
+                                                     lens.ctypes.data, status.ctypes.data,
+                                                     counts.ctypes.data))
+        self.func = None
+        self._keep = keep
+        lens = np.minimum(lens, max_returns)
+        ints = ret_ints(rets)
+        out = [[int(x) for x in ints[i][:lens[i]]] if status[i] == 0 else [] for i in range(self.n)]
+        return out, status, counts
 
     def total_costs(self):
         """Each instance's gas total (WasmEdge_BatchGetTotalCosts)."""

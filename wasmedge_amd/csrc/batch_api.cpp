@@ -429,17 +429,26 @@ uint8_t layout_trial(WasmEdge_BatchContext *C, double secs) {
   double sum = 0;
   for (uint64_t c : cnt) sum += double(c);
   const double rate = sum / secs;
+  // (per-instance calls: the same call vector on the same arguments, not one function)
+  const uint64_t key = C->calls_on ? C->args_fp | (1ull << 63) : uint64_t(uint32_t(C->func));
   if (C->trial == 1) {
     C->trial_rate = rate;
-    C->trial_func = C->func;
+    C->trial_key = key;
     C->trial = 2;
   } else {   // 3
-    C->trial = C->func == C->trial_func && rate >= 1.10 * C->trial_rate ? 0 : 4;
+    // other work than the first measurement ran gives no verdict: back to the module's
+    // granule, and (call vectors, which a caller may well alternate) measure again
+    C->trial_again = key != C->trial_key && ((key | C->trial_key) >> 63) && C->trial_redo < 2;
+    C->trial =key == C->trial_key && rate >= 1.10 * C->trial_rate ? 0 : 4;
   }
   return 0;
 }
 
 uint32_t cells_of_value(uint8_t t) { return wb::cells_of(t); }
+
+// launch_once's entry_pc for per-instance calls (KParams::calls names each lane's): no
+// function's pc, so a wave order learned from one function is never taken for a call vector
+constexpr uint32_t kCallsPc = 0xFFFFFFFEu;
 
 // One interpreter launch over every instance: entry_pc with the staged params (or the
 // start function when is_start). Shared by BatchRun and BatchReset.
@@ -477,6 +486,7 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
   k.entry_pc = entry_pc;
   k.param_cells = is_start ? 0 : C->param_cells;
   k.result_cells = is_start ? 0 : C->result_cells;
+  k.calls = !is_start && C->calls_on ? C->calls.ptr : nullptr;
   k.global_cells = P.global_cells;
   k.total_cells = P.total_cells() ? P.total_cells() : 1;
   k.table_size = uint32_t(P.table0.size());
@@ -555,7 +565,9 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
       // (WB_ORDER_ANY=1: also on other arguments -- an experiment, the per-slot cost of the
       // last launch as the guess)
       const char *oae = getenv("WB_ORDER_ANY");
-      const bool any_args = oae && oae[0] == '1';
+      // (per-instance calls: entry_pc is kCallsPc and the fingerprint covers the call
+      // vector, so an order is reused only for an equal vector on equal arguments)
+      const bool any_args = oae && oae[0] == '1' && !k.calls;
       k.wave_order = C->order_pc == entry_pc && (C->order_fp == C->args_fp || any_args) && C->trial != 1 &&
                              C->trial != 3
                          ? C->wave_order.ptr : nullptr;
@@ -756,6 +768,109 @@ WasmEdge_Result WasmEdge_BatchSetArgs(WasmEdge_BatchContext *C, const WasmEdge_S
   C->param_cells = pc;
   C->result_cells = rc;
   C->result_types = t.results;
+  C->calls_on = false;   // (back to one function for every instance)
+  return R(0);
+}
+
+// Per-instance calls: N independent VMExecute calls (vm.cpp:287-308 resolves each name,
+// executor.cpp:88-100 checks each signature), so an unknown name or a mismatch is that
+// instance's outcome, not the call's. Everything is checked and packed before anything of
+// the context changes: a failed call leaves the previous staging as it was.
+WasmEdge_Result WasmEdge_BatchSetCalls(WasmEdge_BatchContext *C, const WasmEdge_String *FuncNames,
+                                       const uint32_t NumFuncs, const uint32_t *FuncOf,
+                                       const WasmEdge_Value *Params, const uint32_t ParamStride,
+                                       const uint32_t *ParamLens) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!FuncOf || (NumFuncs && !FuncNames)) return R(C->fail(kWrongVMWorkflow, "BatchSetCalls: null FuncOf / FuncNames"));
+  for (uint32_t i = 0; i < C->n; i++)
+    if (FuncOf[i] != WASMEDGE_BATCH_NO_CALL && FuncOf[i] >= NumFuncs)
+      return R(C->fail(kWrongVMWorkflow, "BatchSetCalls: FuncOf[" + std::to_string(i) + "] names no function"));
+  if (!C->shards.empty()) return wbm::set_calls(C, FuncNames, NumFuncs, FuncOf, Params, ParamStride, ParamLens);
+  DevScope dev(C);
+  const wb::Program &P = C->prog;
+  std::vector<int> fidx(NumFuncs, -1);
+  std::vector<uint32_t> fpc(NumFuncs, 0), frc(NumFuncs, 0);
+  for (uint32_t j = 0; j < NumFuncs; j++) {
+    fidx[j] = wb::find_export(P, std::string(FuncNames[j].Buf ? FuncNames[j].Buf : "", FuncNames[j].Length));
+    if (fidx[j] < 0) continue;
+    const wb::FuncType &t = P.types[P.funcs[fidx[j]].type];
+    for (uint8_t ty : t.params) fpc[j] += cells_of_value(ty);
+    for (uint8_t ty : t.results) frc[j] += cells_of_value(ty);
+  }
+  // each instance's function, or the status it sits the run out with
+  std::vector<int32_t> cfunc(C->n, -1);
+  std::vector<uint8_t> cstat(C->n, 0);
+  uint32_t pc = 0, rc = 0;
+  bool import = false;
+  for (uint32_t i = 0; i < C->n; i++) {
+    const uint32_t j = FuncOf[i];
+    if (j == WASMEDGE_BATCH_NO_CALL) continue;
+    if (fidx[j] < 0) { cstat[i] = kFuncNotFound; continue; }
+    const wb::FuncType &t = P.types[P.funcs[fidx[j]].type];
+    const uint32_t len = ParamLens ? ParamLens[i] : ParamStride;
+    bool ok = len == t.params.size() && len <= ParamStride && (len == 0 || Params);
+    for (uint32_t k = 0; ok && k < len; k++) ok = uint8_t(Params[size_t(i) * ParamStride + k].Type) == t.params[k];
+    if (!ok) { cstat[i] = kFuncSigMismatch; continue; }
+    cfunc[i] = fidx[j];
+    pc = std::max(pc, fpc[j]);
+    rc = std::max(rc, frc[j]);
+    import |= P.funcs[fidx[j]].imported;
+  }
+  std::vector<uint32_t> cells(size_t(C->n) * (pc ? pc : 1)), tab(size_t(C->n) * 2);
+  for (uint32_t i = 0; i < C->n; i++) {
+    tab[2 * i] = WB_CALL_SKIP | cstat[i];
+    tab[2 * i + 1] = 0;
+    if (cfunc[i] < 0) continue;
+    const wb::FuncInfo &F = P.funcs[cfunc[i]];
+    const wb::FuncType &t = P.types[F.type];
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < t.params.size(); k++) {
+      const WasmEdge_Value &v = Params[size_t(i) * ParamStride + k];
+      bool full = false;
+      const uint128_t x = t.params[k] == wb::EXTERNREF ? uint128_t(C->xref_in(v.Value, &full)) : v.Value;
+      if (full) return R(C->fail(kRuntimeError, "externref intern table full (2^31 - 1 values)"));
+      for (uint32_t q = 0; q < cells_of_value(t.params[k]); q++)
+        cells[size_t(i) * pc + at++] = uint32_t(x >> (32 * q));
+    }
+    tab[2 * i] = F.imported ? WB_CALL_SKIP : F.entry_pc;   // (an import: BatchRun refuses)
+    tab[2 * i + 1] = at;
+  }
+  const size_t rn = size_t(C->n) * (rc ? rc : 1);
+  if ((C->params.n != cells.size() || !C->params.ptr) && !C->params.alloc(cells.size()))
+    return R(C->fail(kRuntimeError, "device allocation failed"));
+  if ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))
+    return R(C->fail(kRuntimeError, "device allocation failed"));
+  if (!C->calls.ptr && !C->calls.alloc(tab.size())) return R(C->fail(kRuntimeError, "device allocation failed"));
+  if (!C->hip_ok(hipMemcpyAsync(C->params.ptr, cells.data(), cells.size() * 4, hipMemcpyHostToDevice,
+                                C->stream), "params upload") ||
+      !C->hip_ok(hipMemcpyAsync(C->calls.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice,
+                                C->stream), "calls upload") ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "params upload"))
+    return R(kRuntimeError);
+  // fingerprint of the call vector and the arguments (wave order, layout trial)
+  uint64_t fp = 0xC2B2AE3D27D4EB4Full;
+  for (uint32_t c : tab) fp = (fp ^ c) * 0x100000001B3ull + (fp >> 29);
+  for (uint32_t c : cells) fp = (fp ^ c) * 0x100000001B3ull + (fp >> 29);
+  C->args_fp = fp;
+  C->func = -1;
+  C->param_cells = pc;
+  C->result_cells = rc;
+  C->result_types.clear();
+  C->call_func.swap(cfunc);
+  C->call_status.swap(cstat);
+  C->calls_import = import;
+  C->calls_on = true;
+  return R(0);
+}
+
+WasmEdge_Result WasmEdge_BatchGetReturnLens(WasmEdge_BatchContext *C, uint32_t *ReturnLens) {
+  if (!C || !ReturnLens) return R(kWrongVMWorkflow);
+  if (!C->shards.empty()) return wbm::return_lens(C, ReturnLens);
+  if (!C->calls_on && C->func < 0) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs / BatchSetCalls not called"));
+  for (uint32_t i = 0; i < C->n; i++)
+    ReturnLens[i] = !C->calls_on ? uint32_t(C->result_types.size())
+                    : C->call_func[i] < 0 ? 0u
+                    : uint32_t(C->prog.types[C->prog.funcs[C->call_func[i]].type].results.size());
   return R(0);
 }
 
@@ -768,6 +883,11 @@ WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeco
     const uint8_t e = relayout(C, C->trial_mlog[C->trial == 2 ? 1 : 0]);
     if (e) return R(e);
     C->trial = C->trial == 2 ? 3 : 0;
+    if (C->trial == 0 && C->trial_again) {   // (no verdict: the next run measures again)
+      C->trial_again = false;
+      C->trial_redo++;
+      C->trial = 1;
+    }
   }
   // lanes grew into pool rows: the layout takes every page they reached (hostcall.cpp
   // grow_layout; this Reset rewrites every page, so nothing is copied)
@@ -866,12 +986,13 @@ WasmEdge_Result WasmEdge_BatchRun(WasmEdge_BatchContext *C, double *KernelSecond
   if (!C) return R(kWrongVMWorkflow);
   if (!C->shards.empty()) return wbm::run(C, KernelSeconds);
   DevScope dev(C);
-  if (C->func < 0) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs not called"));
-  const wb::FuncInfo &F = C->prog.funcs[C->func];
-  if (F.imported) return R(C->fail(kRuntimeError, "exported function is a host import"));
+  if (C->func < 0 && !C->calls_on) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs not called"));
+  if (C->calls_on ? C->calls_import : C->prog.funcs[C->func].imported)
+    return R(C->fail(kRuntimeError, "exported function is a host import"));
   const bool measure = C->trial == 1 || C->trial == 3;
   double ks = 0;
-  uint8_t e = launch_exec(C, F.entry_pc, false, KernelSeconds || measure ? &ks : nullptr);
+  uint8_t e = launch_exec(C, C->calls_on ? kCallsPc : C->prog.funcs[C->func].entry_pc, false,
+                          KernelSeconds || measure ? &ks : nullptr);
   if (e) return R(e);
   if (KernelSeconds) *KernelSeconds = ks;
   if (C->trial == 5) C->trial = 1;   // (the warm-up run of the layout trial)
@@ -899,10 +1020,18 @@ WasmEdge_Result WasmEdge_BatchResults(WasmEdge_BatchContext *C, WasmEdge_Value *
     if (rc && !C->hip_ok(hipMemcpy(cells.data(), C->results.ptr, cells.size() * 4,
                                    hipMemcpyDeviceToHost), "results"))
       return R(kRuntimeError);
+    // (per-instance calls: each row carries its own function's result types, and an instance
+    // that sat the run out a row of zeroes -- the device wrote nothing there)
+    static const std::vector<uint8_t> none;
     for (uint32_t i = 0; i < C->n; i++) {
+      const std::vector<uint8_t> &types = !C->calls_on ? C->result_types
+                                          : C->call_func[i] < 0 ? none
+                                          : C->prog.types[C->prog.funcs[C->call_func[i]].type].results;
+      if (C->calls_on)
+        for (uint32_t k = uint32_t(types.size()); k < ReturnLen; k++) Returns[size_t(i) * ReturnLen + k] = WasmEdge_Value{};
       uint32_t at = 0;
-      for (uint32_t k = 0; k < C->result_types.size(); k++) {
-        uint8_t ty = C->result_types[k];
+      for (uint32_t k = 0; k < types.size(); k++) {
+        uint8_t ty = types[k];
         uint128_t v = 0;
         for (uint32_t q = 0; q < cells_of_value(ty); q++)
           v |= uint128_t(cells[size_t(i) * rc + at++]) << (32 * q);
@@ -927,6 +1056,21 @@ WasmEdge_Result WasmEdge_BatchExecute(WasmEdge_BatchContext *C, const WasmEdge_S
   r = WasmEdge_BatchRun(C, nullptr);
   if (r.Code) return r;
   return WasmEdge_BatchResults(C, Returns, ReturnLen, PerInstance, InstrCounts);
+}
+
+WasmEdge_Result WasmEdge_BatchExecuteCalls(WasmEdge_BatchContext *C, const WasmEdge_String *FuncNames,
+                                           const uint32_t NumFuncs, const uint32_t *FuncOf,
+                                           const WasmEdge_Value *Params, const uint32_t ParamStride,
+                                           const uint32_t *ParamLens, WasmEdge_Value *Returns,
+                                           const uint32_t ReturnStride, uint32_t *ReturnLens,
+                                           uint8_t *PerInstance, uint64_t *InstrCounts) {
+  if (!C) return R(kWrongVMWorkflow);
+  WasmEdge_Result r = WasmEdge_BatchSetCalls(C, FuncNames, NumFuncs, FuncOf, Params, ParamStride, ParamLens);
+  if (r.Code) return r;
+  r = WasmEdge_BatchRun(C, nullptr);
+  if (r.Code) return r;
+  if (ReturnLens && (r = WasmEdge_BatchGetReturnLens(C, ReturnLens)).Code) return r;
+  return WasmEdge_BatchResults(C, Returns, ReturnStride, PerInstance, InstrCounts);
 }
 
 WasmEdge_Result WasmEdge_BatchMemoryHash(WasmEdge_BatchContext *C, uint64_t *Hashes) {

@@ -97,7 +97,13 @@ struct WasmEdge_BatchContext {
   // 3 = the next run measures that, 4 = the next Reset switches back; 0 = decided
   uint8_t trial = 0;
   uint32_t trial_mlog[2] = {0, 0};   // (the module's granule, the other one)
-  int trial_func = -1;
+  // what the first measurement ran: the function, or for per-instance calls the fingerprint
+  // of the call vector and its arguments (bit 63 set). A second measurement on other work
+  // gives no verdict: with calls on either side the trial is taken again (trial_redo counts
+  // them; after 2 the module's granule stays, undecided)
+  uint64_t trial_key = ~0ull;
+  uint8_t trial_redo = 0;
+  bool trial_again = false;          // the Reset that switches back starts the next trial
   double trial_rate = 0;
   bool frame_hbm = false;         // frames in HBM (wb_exec_hbm_kernel), KParams::hframe
   DevBuf<uint32_t> hframe;
@@ -116,6 +122,7 @@ struct WasmEdge_BatchContext {
   // ids put them. Scheduling only: results never depend on it (WB_LPT=0 turns it off).
   DevBuf<uint32_t> wave_ticks, wave_order;
   uint32_t order_pc = 0xFFFFFFFFu;   // entry pc of the launch the order was taken from
+                                     // (kCallsPc: per-instance calls, their vector in the fp)
   uint64_t order_fp = 0, args_fp = 1;   // its arguments' fingerprint; the staged arguments'
   bool lpt = true;
   uint32_t sched = 1;             // KParams::sched (WB_SCHED=k; 0: min-pc scheduling only)
@@ -201,7 +208,15 @@ struct WasmEdge_BatchContext {
   int func = -1;
   uint32_t param_cells = 0, result_cells = 0;
   std::vector<uint8_t> result_types;
-  bool ran = false;         // a Run completed since the last Reset (results are valid)
+  // per-instance calls (WasmEdge_BatchSetCalls; a plain SetArgs clears calls_on): the device
+  // table (KParams::calls), each instance's function (-1: it sits the run out, with
+  // call_status) and whether a named export is a host import (BatchRun then fails as for a
+  // uniform one); param_cells / result_cells are the row strides
+  bool calls_on = false, calls_import = false;
+  DevBuf<uint32_t> calls;
+  std::vector<int32_t> call_func;
+  std::vector<uint8_t> call_status;
+  bool ran = false;        // a Run completed since the last Reset (results are valid)
   bool mem_fresh = true;    // memory never initialised: the next Reset writes every page
   // A Reset that skipped its host sync left init kernels queued on `stream` (non-blocking,
   // so NOT ordered before the host accessors' synchronous null-stream copies): every host

@@ -397,6 +397,20 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
   for (uint32_t c = 0; c < p.global_cells; c++) F.set(c, LS(LS_GLOBALS + c));
   uint32_t ycall = 0, ybase = 0;   // host import being called when the lane yields
   bool active = inst < p.n;   // the lane has an instance (partial waves)
+  // per-instance calls (KParams::calls): the lane's own entry pc, or it sits the launch out
+  // with its final status from the start, never running -- like a lane past n, in any lane
+  // of the wave. It stays `active` only for the epilogue, which writes that status, the
+  // count 0 and the instance state back as it was read (a resume round finds it not parked
+  // and leaves it alone). No prologue or engine reads its params or frame.
+  if (p.calls && !p.resume && active) {
+    const uint32_t e = p.calls[2u * inst];
+    if (e >= WB_CALL_SKIP) {
+      status = e & 0xFFu;
+      if (fs) LS(LS_RPC) = 0xFFFFFFFFu;
+    } else {
+      pc = e;
+    }
+  }
   if (p.resume) {
     // continue a lane parked at a host import: frame from fsave, the host function's
     // results (hcall = their cell count, ~0 = the host ended the lane) into its cells
@@ -419,7 +433,12 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
   } else if (status == WB_STATUS_RUNNING) {
     if (fs) LS(LS_RPC) = 0xFFFFFFFFu;   // a fresh invocation: nothing parked
     const uint32_t *prm = p.params + (size_t)inst * p.param_cells;
-    for (uint32_t c = 0; c < p.param_cells; c++) F.set(p.global_cells + c, prm[c]);
+    if (!p.calls) {
+      for (uint32_t c = 0; c < p.param_cells; c++) F.set(p.global_cells + c, prm[c]);
+    } else {   // (only its function's cells: the rest of the row is not its to read)
+      const uint32_t nc = p.calls[2u * inst + 1u];
+      for (uint32_t c = 0; c < nc; c++) F.set(p.global_cells + c, prm[c]);
+    }
     GS_WR(0u, DBC_EXIT_PC);   // return record of the entry frame: pc = EXIT
     gsp = 1;
   }

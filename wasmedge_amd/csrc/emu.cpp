@@ -137,24 +137,14 @@ __attribute__((visibility("default"))) uint32_t wb_emu_wasi_exit_code(uint32_t i
   return inst < g_wasi_lanes.size() ? g_wasi_lanes[inst].exit_code : 0;
 }
 
-// Returns ErrCode of the call; per-instance outputs like WasmEdge_BatchExecute.
-// params: [n][param cells] u32; results: [n][result cells] u32.
-__attribute__((visibility("default"))) int wb_emu_execute(
-    const uint8_t *wasm, uint32_t len, const char *func, uint32_t n, const uint32_t *params,
-    uint32_t *results, uint8_t *statuses, uint64_t *counts, uint64_t *hashes,
-    uint32_t max_pages, uint32_t gs_depth, uint64_t max_steps) {
-  wb::Program P;
-  uint8_t ec = 0;
-  g_err = wb::load_program(wasm, len, P, &ec, g_cost_limit != ~0ull, &g_imports, g_tail_call,
-                           g_multi_memory);
-  if (!g_err.empty()) return ec ? ec : 2;
-  int f = wb::find_export(P, func);
-  if (f < 0) { g_err = "function not found"; return 0x05; }
-  const wb::FuncInfo &F = P.funcs[f];
-  const wb::FuncType &T = P.types[F.type];
-  uint32_t pcells = 0, rcells = 0;
-  for (uint8_t t : T.params) pcells += wb::cells_of(t);
-  for (uint8_t t : T.results) rcells += wb::cells_of(t);
+// n fresh instances of P, one after the other: each runs the function at `entry` on the
+// pcells cells of its row of params -- or, with `calls` (as KParams::calls), its own entry
+// on its own cells, pcells / rcells being the row strides; an instance whose entry is
+// >= WB_CALL_SKIP is instantiated and not invoked (that status, count 0).
+static int emu_core(wb::Program &P, uint32_t entry, const uint32_t *calls, uint32_t pcells, uint32_t rcells,
+                    uint32_t n, const uint32_t *params, uint32_t *results, uint8_t *statuses,
+                    uint64_t *counts, uint64_t *hashes, uint32_t max_pages, uint32_t gs_depth,
+                    uint64_t max_steps) {
   // page limit as the library's (memory.h:88-115): 65536, the module's max, max_pages
   uint32_t limit = 65536;
   if (P.mem_has_max) limit = std::min(limit, P.mem_max);
@@ -378,8 +368,11 @@ __attribute__((visibility("default"))) int wb_emu_execute(
       status = invoke(P.funcs[P.start_func].entry_pc, nullptr, 0, start_count);
       p.result_cells = rcells;
     }
-    if (status == WB_STATUS_OK)
-      status = invoke(F.entry_pc, params + size_t(inst) * pcells, pcells, count);
+    if (status == WB_STATUS_OK) {
+      const uint32_t e = calls ? calls[2 * inst] : entry;
+      if (e >= WB_CALL_SKIP) status = e & 0xFFu;
+      else status = invoke(e, params + size_t(inst) * pcells, calls ? calls[2 * inst + 1] : pcells, count);
+    }
     statuses[inst] = uint8_t(status);
     counts[inst] = count;
     g_costs[inst] = cost;
@@ -393,6 +386,74 @@ __attribute__((visibility("default"))) int wb_emu_execute(
     }
   }
   return 0;
+}
+
+// Returns ErrCode of the call; per-instance outputs like WasmEdge_BatchExecute.
+// params: [n][param cells] u32; results: [n][result cells] u32.
+__attribute__((visibility("default"))) int wb_emu_execute(
+    const uint8_t *wasm, uint32_t len, const char *func, uint32_t n, const uint32_t *params,
+    uint32_t *results, uint8_t *statuses, uint64_t *counts, uint64_t *hashes,
+    uint32_t max_pages, uint32_t gs_depth, uint64_t max_steps) {
+  wb::Program P;
+  uint8_t ec = 0;
+  g_err = wb::load_program(wasm, len, P, &ec, g_cost_limit != ~0ull, &g_imports, g_tail_call,
+                           g_multi_memory);
+  if (!g_err.empty()) return ec ? ec : 2;
+  int f = wb::find_export(P, func);
+  if (f < 0) { g_err = "function not found"; return 0x05; }
+  const wb::FuncType &T = P.types[P.funcs[f].type];
+  uint32_t pcells = 0, rcells = 0;
+  for (uint8_t t : T.params) pcells += wb::cells_of(t);
+  for (uint8_t t : T.results) rcells += wb::cells_of(t);
+  return emu_core(P, P.funcs[f].entry_pc, nullptr, pcells, rcells, n, params, results, statuses, counts,
+                  hashes, max_pages, gs_depth, max_steps);
+}
+
+// WasmEdge_BatchExecuteCalls' semantics on fresh instances: instance i calls
+// funcs[func_of[i]] (0xFFFFFFFF: no call) with plens[i] values of the types in its row of
+// ptypes ([n][pstride] valtypes), their cells packed from the start of its row of params
+// ([n][pcstride] u32). An unknown name gives that instance 0x05, a count or type mismatch
+// 0x83; neither runs, nor does a no-call instance (status 0): count 0, results zeroed.
+// results: [n][rcstride] u32 (rcstride at least the widest called function's result cells,
+// else 0x04); rlens[i] = its function's result count. A func_of[i] naming no entry of
+// funcs is 0x04.
+__attribute__((visibility("default"))) int wb_emu_execute_calls(
+    const uint8_t *wasm, uint32_t len, const char *const *funcs, uint32_t nfuncs, const uint32_t *func_of,
+    uint32_t n, const uint32_t *params, uint32_t pcstride, const uint8_t *ptypes, uint32_t pstride,
+    const uint32_t *plens, uint32_t *results, uint32_t rcstride, uint32_t *rlens, uint8_t *statuses,
+    uint64_t *counts, uint64_t *hashes, uint32_t max_pages, uint32_t gs_depth, uint64_t max_steps) {
+  wb::Program P;
+  uint8_t ec = 0;
+  g_err = wb::load_program(wasm, len, P, &ec, g_cost_limit != ~0ull, &g_imports, g_tail_call,
+                           g_multi_memory);
+  if (!g_err.empty()) return ec ? ec : 2;
+  for (uint32_t i = 0; i < n; i++)
+    if (func_of[i] != 0xFFFFFFFFu && func_of[i] >= nfuncs) { g_err = "func_of names no function"; return 0x04; }
+  std::vector<uint32_t> calls(size_t(n) * 2, 0u);
+  for (uint32_t i = 0; i < n; i++) {
+    calls[2 * i] = WB_CALL_SKIP;
+    if (rlens) rlens[i] = 0;
+    if (func_of[i] == 0xFFFFFFFFu) continue;
+    const int f = wb::find_export(P, funcs[func_of[i]]);
+    if (f < 0) { calls[2 * i] = WB_CALL_SKIP | 0x05u; continue; }
+    if (P.funcs[f].imported) { g_err = "exported function is a host import"; return 0x02; }
+    const wb::FuncType &T = P.types[P.funcs[f].type];
+    bool ok = plens[i] == T.params.size() && plens[i] <= pstride;
+    uint32_t pc = 0, rc = 0;
+    for (uint32_t k = 0; ok && k < plens[i]; k++) {
+      ok = ptypes[size_t(i) * pstride + k] == T.params[k];
+      pc += wb::cells_of(T.params[k]);
+    }
+    if (!ok) { calls[2 * i] = WB_CALL_SKIP | 0x83u; continue; }
+    for (uint8_t t : T.results) rc += wb::cells_of(t);
+    if (pc > pcstride || rc > rcstride) { g_err = "row stride below a called function's cells"; return 0x04; }
+    calls[2 * i] = P.funcs[f].entry_pc;
+    calls[2 * i + 1] = pc;
+    if (rlens) rlens[i] = uint32_t(T.results.size());
+  }
+  for (size_t k = 0; k < size_t(n) * rcstride; k++) results[k] = 0u;
+  return emu_core(P, 0, calls.data(), pcstride, rcstride, n, params, results, statuses, counts, hashes,
+                  max_pages, gs_depth, max_steps);
 }
 
 // Disassemble the lowered program (debugging / tests of the lowering).

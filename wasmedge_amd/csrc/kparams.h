@@ -118,7 +118,14 @@ struct KParams {
   uint32_t rf_on, rf_image_words, rf_init_words, rf_init_pages, rf_init_dropped;
   const uint32_t *rf_image, *rf_global_init;
   uint64_t rf_init_cost;
+  // per-instance calls (WasmEdge_BatchSetCalls), else NULL and every lane runs entry_pc with
+  // param_cells cells: calls[2i] = instance i's entry pc, calls[2i + 1] = its function's
+  // parameter cells (the first of its row of `params`; param_cells / result_cells are then
+  // the row strides). An entry >= WB_CALL_SKIP: the instance sits the launch out with the
+  // status in its low byte (0: no call; FuncNotFound, FuncSigMismatch), like a lane past n.
+  const uint32_t *calls;
 };
+#define WB_CALL_SKIP 0xFFFFFF00u
 
 // Per-lane instance state that persists across invocations until the next Reset (the
 // reference keeps it in ModuleInstance / MemoryInstance / GlobalInstance): memory size,

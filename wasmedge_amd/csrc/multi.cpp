@@ -169,6 +169,39 @@ WasmEdge_Result set_args(Ctx *C, const WasmEdge_String name, const WasmEdge_Valu
   });
 }
 
+// Every shard stages its own instances' calls under the same names; a shard that fails
+// (externref interning, device memory) fails the call.
+WasmEdge_Result set_calls(Ctx *C, const WasmEdge_String *names, uint32_t nnames, const uint32_t *func_of,
+                          const WasmEdge_Value *params, uint32_t stride, const uint32_t *plens) {
+  std::vector<WasmEdge_Value> rows;
+  std::vector<uint32_t> fo, pl;
+  return each(C, [&](Ctx *s) {
+    rows.assign(size_t(s->n) * stride, WasmEdge_Value{});
+    fo.assign(s->n, WASMEDGE_BATCH_NO_CALL);
+    pl.assign(s->n, stride);
+    for (uint32_t i = 0; i < s->n; i++) {
+      const uint32_t g = s->gid(i);
+      fo[i] = func_of[g];
+      if (plens) pl[i] = plens[g];
+      if (params)
+        std::copy(params + size_t(g) * stride, params + size_t(g + 1) * stride,
+                  rows.begin() + ptrdiff_t(size_t(i) * stride));
+    }
+    return WasmEdge_BatchSetCalls(s, names, nnames, fo.data(), params && stride ? rows.data() : nullptr,
+                                  stride, pl.data());
+  });
+}
+
+WasmEdge_Result return_lens(Ctx *C, uint32_t *lens) {
+  std::vector<uint32_t> v;
+  return each(C, [&](Ctx *s) {
+    v.assign(s->n, 0);
+    const WasmEdge_Result r = WasmEdge_BatchGetReturnLens(s, v.data());
+    if (!r.Code) scatter(s, reinterpret_cast<const uint8_t *>(v.data()), reinterpret_cast<uint8_t *>(lens), 4, 1);
+    return r;
+  });
+}
+
 // Reset / Run: every shard on its own thread; the time is the slowest shard's
 WasmEdge_Result reset(Ctx *C, double *secs) {
   std::vector<double> t(C->shards.size(), 0.0);
@@ -191,7 +224,11 @@ WasmEdge_Result run(Ctx *C, double *secs) {
   if (!r.Code)
     if (Ctx *f = first(C))
       for (Ctx *s : C->shards)
-        if (s && s != f) s->trial = f->trial;
+        if (s && s != f) {
+          s->trial = f->trial;
+          s->trial_again = f->trial_again;   // (call vectors: each shard keys on its slice)
+          s->trial_redo = f->trial_redo;
+        }
   return r;
 }
 

@@ -11,6 +11,11 @@ void destroy(WasmEdge_BatchContext *C);
 bool route(const WasmEdge_BatchContext *C, uint32_t inst, WasmEdge_BatchContext **s, uint32_t *local);
 WasmEdge_Result set_args(WasmEdge_BatchContext *C, const WasmEdge_String name,
                          const WasmEdge_Value *params, uint32_t plen);
+// per-instance calls: FuncOf / Params / ParamLens sliced by the placement (FuncOf checked)
+WasmEdge_Result set_calls(WasmEdge_BatchContext *C, const WasmEdge_String *names, uint32_t nnames,
+                          const uint32_t *func_of, const WasmEdge_Value *params, uint32_t stride,
+                          const uint32_t *plens);
+WasmEdge_Result return_lens(WasmEdge_BatchContext *C, uint32_t *lens);
 WasmEdge_Result reset(WasmEdge_BatchContext *C, double *secs);
 WasmEdge_Result run(WasmEdge_BatchContext *C, double *secs);
 WasmEdge_Result results(WasmEdge_BatchContext *C, WasmEdge_Value *rets, uint32_t rlen, uint8_t *st,
