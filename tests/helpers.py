@@ -41,6 +41,52 @@ def emu_lib():
     return _emu
 
 
+_jit = None
+_JIT_DUMPS = {"plain": "WB_JIT_DUMP", "simt": "WB_JIT_DUMP_SIMT", "trip": "WB_JIT_DUMP_TRIP"}
+
+
+def jit_lib():
+    """the product library, for its CPU test hooks (jit_hooks.cpp)"""
+    global _jit
+    if _jit is None:
+        L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
+        L.wb_jit_check.restype = ctypes.c_int
+        L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
+        _jit = L
+    return _jit
+
+
+def jit_check(wasm, glog, dump=None):
+    """wb_jit_check: lower `wasm`, pick its runs and assemble every flavour for gfx950 without
+    a device. dump: "plain", "simt" or "trip" (or a tuple of them) to get that flavour's
+    generated source back. Returns (runs, instructions, text) -- text None without `dump`,
+    a dict by flavour for a tuple; fails with the hook's error."""
+    import tempfile
+    names = (dump,) if isinstance(dump, str) else tuple(dump or ())
+    err = ctypes.create_string_buffer(4096)
+    ins = ctypes.c_uint32(0)
+    with tempfile.TemporaryDirectory() as tmp:
+        saved = {v: os.environ.get(v) for v in _JIT_DUMPS.values()}
+        try:
+            for v in _JIT_DUMPS.values():
+                os.environ.pop(v, None)
+            for k in names:
+                os.environ[_JIT_DUMPS[k]] = os.path.join(tmp, k + ".s")
+            n = jit_lib().wb_jit_check(wasm, len(wasm), glog, ctypes.byref(ins), err, 4096)
+        finally:
+            for v, old in saved.items():
+                os.environ.pop(v, None)
+                if old is not None:
+                    os.environ[v] = old
+        assert n >= 0, err.value.decode()
+        text = {}
+        for k in names:
+            with open(os.path.join(tmp, k + ".s")) as f:
+                text[k] = f.read()
+    return n, ins.value, (text[dump] if isinstance(dump, str) else text or None)
+
+
 def to_cells(args, types):
     out = []
     for a, t in zip(args, types):

@@ -6,13 +6,11 @@ Both depend on cell liveness, so the module mixes cases that fold with cases tha
 a constant still live after its run, a splat of a non-inline constant, a subtraction
 from the constant (operand order), -0.0 and NaN inputs (whose payload a later store makes
 observable), an any_true result used after its branch. Bit-exact against the oracle."""
-import ctypes
-import os
 
 import pytest
 
 import oracle_py as O
-from helpers import compare, gpu_run, oracle_run
+from helpers import compare, gpu_run, jit_check, oracle_run
 from wasmedge_amd.wat import assemble
 
 I32, I64 = 0x7F, 0x7E
@@ -61,22 +59,10 @@ def rows():
     return [[s, n] for s in (-3, -1, 0, 1, 2, 5, 100, -100, 7) for n in (0, 1, 3, 17, 50)]
 
 
-def test_folds_happen(built, tmp_path):
+def test_folds_happen(built):
     """The module really exercises the folds: its compiled code names the constants."""
-    from wasmedge_amd import batch
-    L = batch.lib()
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    dump = tmp_path / "simt.s"
-    os.environ["WB_JIT_DUMP_SIMT"] = str(dump)
-    try:
-        err = ctypes.create_string_buffer(256)
-        n = ctypes.c_uint32()
-        assert L.wb_jit_check(FOLD, len(FOLD), 7, ctypes.byref(n), err, 256) > 0, err.value
-    finally:
-        del os.environ["WB_JIT_DUMP_SIMT"]
-    src = dump.read_text()
+    n, _, src = jit_check(FOLD, 7, dump="simt")
+    assert n > 0
     assert "4.0" in src and "2.0" in src and "0.5" in src
 
 
@@ -121,22 +107,11 @@ def cmpany_rows():
     return [[s, n] for s in (-3, -1, 0, 1, 2, 5, -100, 7) for n in (0, 1, 5, 17)]
 
 
-def test_cmpany_emitted(built, tmp_path):
+def test_cmpany_emitted(built):
     """The compiled code of CMPANY ORs the compare's two lane masks into the branch."""
-    from wasmedge_amd import batch
-    L = batch.lib()
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    dump = tmp_path / "simt.s"
-    os.environ["WB_JIT_DUMP_SIMT"] = str(dump)
-    try:
-        err = ctypes.create_string_buffer(256)
-        n = ctypes.c_uint32()
-        assert L.wb_jit_check(CMPANY, len(CMPANY), 0, ctypes.byref(n), err, 256) > 0, err.value
-    finally:
-        del os.environ["WB_JIT_DUMP_SIMT"]
-    assert "s_or_b64 vcc, vcc, s[68:69]" in dump.read_text()
+    n, _, src = jit_check(CMPANY, 0, dump="simt")
+    assert n > 0
+    assert "s_or_b64 vcc, vcc, s[68:69]" in src
 
 
 def test_cmpany_rows_on_oracle():

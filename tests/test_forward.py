@@ -9,17 +9,14 @@ cells), misaligned words (no forwarding: every trip leaves to the C++ step), wor
 the one page of memory (every lane traps in the first trip) -- with per-lane trip counts
 so that lanes leave the loop at different trips (the copies' split paths), and check
 every lane against the oracle bit for bit with forwarding on and off."""
-import ctypes
-import os
 
 import pytest
 
 import oracle_py as O
-from helpers import compare, gpu_run
+from helpers import compare, gpu_run, jit_check
 from wasmedge_amd.wat import assemble
 
 I32 = 0x7F
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = [[(i * 2654435761 + 12345) & 0xFFFFFFFF] for i in range(160)]
 CASES = [(64, 96), (64, 68), (64, 66), (65528, 96)]
 
@@ -97,19 +94,8 @@ def random_loop_module(seed):
 
 def _copies(wasm):
     """forwarding copies of the compiled SIMT code (wb_jit_check's dump: labels Lb<k>c)"""
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    path = "/tmp/wb_fwd_%d.s" % os.getpid()
-    os.environ["WB_JIT_DUMP_SIMT"] = path
-    try:
-        err = ctypes.create_string_buffer(4096)
-        assert L.wb_jit_check(wasm, len(wasm), 0, None, err, 4096) >= 0, err.value
-        src = open(path).read()
-        return sum(1 for ln in src.splitlines() if ln.strip().startswith('"Lb') and 'c:' in ln)
-    finally:
-        os.environ.pop("WB_JIT_DUMP_SIMT", None)
+    src = jit_check(wasm, 0, dump="simt")[2]
+    return sum(1 for ln in src.splitlines() if ln.strip().startswith('"Lb') and 'c:' in ln)
 
 
 def test_forwarding_copies(built):

@@ -10,17 +10,14 @@ page of memory on the lanes whose address mask reaches past it (0x88 at the exac
 instruction inside the callee), with the caller's live
 cells at both parities (only even shifts are inlined), and check every lane against the
 oracle bit for bit with inlining on and off."""
-import ctypes
-import os
 
 import pytest
 
 import oracle_py as O
-from helpers import compare, gpu_run
+from helpers import compare, gpu_run, jit_check
 from wasmedge_amd.wat import assemble
 
 I32 = 0x7F
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS = [[(i * 2654435761 + 977) & 0xFFFFFFFF] for i in range(192)]
 
 
@@ -55,18 +52,7 @@ def leaf_module(extra_locals):
 
 def _inlined(wasm):
     """how many call sites the compiled SIMT code inlines (wb_jit_check's dump)"""
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    path = "/tmp/wb_inline_%d.s" % os.getpid()
-    os.environ["WB_JIT_DUMP_SIMT"] = path
-    try:
-        err = ctypes.create_string_buffer(4096)
-        assert L.wb_jit_check(wasm, len(wasm), 0, None, err, 4096) >= 0, err.value
-        return open(path).read().count('"Lii')
-    finally:
-        os.environ.pop("WB_JIT_DUMP_SIMT", None)
+    return jit_check(wasm, 0, dump="simt")[2].count('"Lii')
 
 
 def test_inlined_call_sites(built):

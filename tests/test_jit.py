@@ -20,12 +20,11 @@ import random
 import pytest
 
 import oracle_py as O
-from helpers import compare, gpu_run
+from helpers import compare, gpu_run, jit_check, jit_lib
 from wasmedge_amd import workloads as W
 from wasmedge_amd.wat import assemble
 
 I32, I64 = 0x7F, 0x7E
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N32, N64 = 6, 6
 
 I32_BIN = ["add", "sub", "mul", "and", "or", "xor", "shl", "shr_s", "shr_u", "rotl", "rotr"]
@@ -186,20 +185,9 @@ SEEDS = list(range(12))
 ROWS = [[(i * 2654435761 + 12345) & 0xFFFFFFFF] for i in range(256)]
 
 
-def _check_lib():
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    return L
-
-
 def _jit_check(wasm, glog):
-    err = ctypes.create_string_buffer(4096)
-    ins = ctypes.c_uint32(0)
-    n = _check_lib().wb_jit_check(wasm, len(wasm), glog, ctypes.byref(ins), err, 4096)
-    assert n >= 0, err.value.decode()
-    return n, ins.value
+    n, ins, _ = jit_check(wasm, glog)
+    return n, ins
 
 
 def test_random_modules_run_on_oracle():
@@ -281,7 +269,7 @@ def test_trip_mode_choice(built):
     """Which modules run trip mode (jit.h trips_pay, Program::divergent_mem): C3 (addresses
     from loaded data) and C4 (a br_table state machine, no calls) do; C1 (recursion), C2
     (converged, with calls), C5 (an escape loop whose lanes leave one by one) do not."""
-    L = _check_lib()
+    L = jit_lib()
     L.wb_trip_choice.restype = ctypes.c_int
     L.wb_trip_choice.argtypes = [ctypes.c_char_p, ctypes.c_uint32]
     fib = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fibonacci.wasm"), "rb").read()

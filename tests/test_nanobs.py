@@ -7,20 +7,17 @@ CPU: the analysis removes every fix from C5's module and keeps the fixes of a mo
 returns, stores or reinterprets its NaNs. GPU: such a module, with NaNs made fresh
 (inf - inf, 0 * inf) and propagated from parameters, is bit-exact against the oracle
 (returned payloads, memory hash, globals through a getter) with the analysis on and off."""
-import ctypes
 import math
-import os
 import struct
 
 import pytest
 
 import oracle_py as O
-from helpers import compare, gpu_run, oracle_run
+from helpers import compare, gpu_run, jit_check, oracle_run
 from wasmedge_amd import workloads as W
 from wasmedge_amd.wat import assemble
 
 I32, I64, F64 = 0x7F, 0x7E, 0x7C
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 NAN_WAT = r"""
 (module
@@ -90,30 +87,18 @@ def rows():
     return out
 
 
-def _check_lib():
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32]
-    return L
-
-
-def _nan_checks(wasm, monkeypatch, tmp_path, on):
+def _nan_checks(wasm, monkeypatch, on):
     """v_cmp_u (a NaN fix's test) in the compiled SIMT code of `wasm`"""
-    dump = tmp_path / ("simt_%d.s" % on)
-    monkeypatch.setenv("WB_JIT_DUMP_SIMT", str(dump))
     monkeypatch.setenv("WB_NANOBS", "1" if on else "0")
-    err = ctypes.create_string_buffer(4096)
-    assert _check_lib().wb_jit_check(wasm, len(wasm), 0, None, err, 4096) >= 0, err.value
-    return dump.read_text().count("v_cmp_u_f")
+    return jit_check(wasm, 0, dump="simt")[2].count("v_cmp_u_f")
 
 
-def test_analysis_drops_unobserved_fixes(built, monkeypatch, tmp_path):
+def test_analysis_drops_unobserved_fixes(built, monkeypatch):
     mandel = W.mandel_wasm()
-    assert _nan_checks(mandel, monkeypatch, tmp_path, False) > 0
-    assert _nan_checks(mandel, monkeypatch, tmp_path, True) == 0
+    assert _nan_checks(mandel, monkeypatch, False) > 0
+    assert _nan_checks(mandel, monkeypatch, True) == 0
     m = assemble(NAN_WAT)
-    off, on = _nan_checks(m, monkeypatch, tmp_path, False), _nan_checks(m, monkeypatch, tmp_path, True)
+    off, on = _nan_checks(m, monkeypatch, False), _nan_checks(m, monkeypatch, True)
     assert 0 < on < off   # the loop's fixes go, the observed results' stay
 
 

@@ -13,17 +13,14 @@ straight into the second) and onto the cached word (the `if` before the consumer
 every result, status, instruction count and memory image must still equal the oracle's,
 with either shortcut on or off (WB_TRIP_PF, WB_TRIP_FWD; trip mode forced, WB_TRIP=1).
 """
-import ctypes
-import os
 
 import pytest
 
 import oracle_py as O
-from helpers import compare
+from helpers import compare, jit_check
 from wasmedge_amd import workloads as W
 from wasmedge_amd.wat import assemble
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32 = 0x7F
 
 SCANS_WAT = r"""
@@ -126,17 +123,10 @@ def rows():
     return [[s, n] for s in range(256) for n in (0, 1, 2, 5, 9, 16, 33, 60)]
 
 
-def _trip_dump(wasm, tmp_path, monkeypatch):
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    dump = tmp_path / "trip.s"
-    monkeypatch.setenv("WB_JIT_DUMP_TRIP", str(dump))
-    err = ctypes.create_string_buffer(4096)
-    ins = ctypes.c_uint32(0)
-    assert L.wb_jit_check(wasm, len(wasm), 7, ctypes.byref(ins), err, 4096) > 0, err.value
-    return dump.read_text()
+def _trip_dump(wasm):
+    n, _, src = jit_check(wasm, 7, dump="trip")
+    assert n > 0
+    return src
 
 
 def test_module_runs_on_oracle():
@@ -147,15 +137,15 @@ def test_module_runs_on_oracle():
 
 
 @pytest.mark.parametrize("name", ["c3", "scans"])
-def test_trip_code_has_both_shortcuts(built, tmp_path, monkeypatch, name):
+def test_trip_code_has_both_shortcuts(built, monkeypatch, name):
     """C3 and the test module compile a prefetched second scan (LtS) and a consumer of the
     cached words (LtF); WB_TRIP_PF=0 / WB_TRIP_FWD=0 drop them."""
     wasm = W.qsort_wasm() if name == "c3" else scans_wasm()
-    src = _trip_dump(wasm, tmp_path, monkeypatch)
+    src = _trip_dump(wasm)
     assert "LtS" in src and "LtF" in src and "_pf:" in src
     monkeypatch.setenv("WB_TRIP_PF", "0")
     monkeypatch.setenv("WB_TRIP_FWD", "0")
-    src = _trip_dump(wasm, tmp_path, monkeypatch)
+    src = _trip_dump(wasm)
     assert "LtS" not in src and "LtF" not in src
 
 
@@ -182,15 +172,15 @@ def test_gpu_shortcuts_exact(built, monkeypatch, pf, fwd):
     assert compare(ref, got, st, cnt, h, [I32], exact=True) == []
 
 
-def test_machine_threads_its_dispatch(built, tmp_path, monkeypatch):
+def test_machine_threads_its_dispatch(built, monkeypatch):
     """the state runs' jumps take the br_table themselves: a state with a computed next
     state carries a copy of the table's compare chain (v_min_u32 clamps its index), one
     with a constant next state jumps straight on; WB_BRT_THREAD=0 leaves the dispatch run's
     chain alone"""
     for wasm, copies in ((W.collatz_wasm(), 1), (machine_wasm(), 2)):
-        on = _trip_dump(wasm, tmp_path, monkeypatch).count("v_min_u32")
+        on = _trip_dump(wasm).count("v_min_u32")
         monkeypatch.setenv("WB_BRT_THREAD", "0")
-        off = _trip_dump(wasm, tmp_path, monkeypatch).count("v_min_u32")
+        off = _trip_dump(wasm).count("v_min_u32")
         monkeypatch.delenv("WB_BRT_THREAD")
         assert on - off == copies
     m = O.Module(machine_wasm())

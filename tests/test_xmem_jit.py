@@ -9,17 +9,14 @@ pages) and an out-of-bounds one leave before the instruction and the C++ step ex
 compare every lane with the oracle's restatement on the compiled runs (SIMT and trip mode)
 and on the threaded core alone (WB_JIT=0); the results fold in memories 1 and 2 (the memory
 hash covers memory 0)."""
-import ctypes
-import os
 
 import pytest
 
 import oracle_py as O
-from helpers import compare, emu_run
+from helpers import compare, emu_run, jit_check
 from wasmedge_amd.wat import assemble
 from wasmedge_amd import workloads as W
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32 = 0x7F
 
 # every load and store width on memories 1 (1 page, max 4) and 2 (2 pages), sub-word
@@ -122,14 +119,6 @@ def rows():
     return [[s, n] for s in range(256) for n in (0, 3, 40, 150)]
 
 
-def _check_lib():
-    L = ctypes.CDLL(os.path.join(ROOT, "wasmedge_amd", "libwasmedge_batch.so"))
-    L.wb_jit_check.restype = ctypes.c_int
-    L.wb_jit_check.argtypes = [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
-                               ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_uint32]
-    return L
-
-
 def test_module_runs_on_oracle():
     """the rows end both ways: results, and the trap past memory 1"""
     m = O.Module(xj_wasm(), multi_memory=True)
@@ -147,17 +136,14 @@ def test_emulator_matches_oracle(built):
 
 
 @pytest.mark.parametrize("name", ["xj", "c3x"])
-def test_accesses_compile(built, tmp_path, monkeypatch, name):
+def test_accesses_compile(built, name):
     """every flavour of the compiled runs (plain, SIMT, trip) compiles the extra-memory
     accesses: their code addresses the wave's block through s[98:99]"""
     wasm = xj_wasm() if name == "xj" else W.qsort_x_wasm()
-    for k in ("", "_SIMT", "_TRIP"):
-        monkeypatch.setenv("WB_JIT_DUMP" + k, str(tmp_path / ("d%s.s" % k)))
-    err = ctypes.create_string_buffer(4096)
-    n = ctypes.c_uint32()
-    assert _check_lib().wb_jit_check(wasm, len(wasm), 0, ctypes.byref(n), err, 4096) > 0, err.value
-    for k in ("", "_SIMT", "_TRIP"):
-        assert "s[98:99]" in (tmp_path / ("d%s.s" % k)).read_text(), k
+    n, _, text = jit_check(wasm, 0, dump=("plain", "simt", "trip"))
+    assert n > 0
+    for k in ("plain", "simt", "trip"):
+        assert "s[98:99]" in text[k], k
 
 
 def _gpu_rows(wasm, func, rs, env, monkeypatch, reps=2):

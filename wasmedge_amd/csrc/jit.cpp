@@ -8,9 +8,6 @@
 // numbers and immediates folded in; instruction semantics: dbc_step.inc.
 #include "jit.h"
 
-#include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-
 #include <algorithm>
 #include <cctype>
 #include <cstdarg>
@@ -18,13 +15,13 @@
 #include <cstdlib>
 #include <functional>
 #include <map>
-#include <mutex>
-#include <tuple>
 
 #include "frontend.h"
+#include "jit_int.h"
 #include "tc_slots.h"
 
 namespace wb {
+using namespace jit;
 
 namespace {
 
@@ -69,14 +66,45 @@ uint16_t xmop(const DInstr &I) {
   const uint16_t op = uint16_t(I.w0 & 0x7FFFu);
   return op == OP_XLD || op == OP_XST ? uint16_t(I.w2 >> 16) : uint16_t(0);
 }
-// The word offsets of the extra memories in a lane's block (batch_ctx.h xinfo_h: memory k
-// at word xinfo[2 (k - 1)]), for the jit_source call that is compiling (null in dry runs)
-thread_local const std::vector<uint32_t> *g_xinfo = nullptr;
-thread_local uint32_t g_xlog = 0;   // (their granule: 4 << g_xlog bytes, KParams::xlog)
-// the first memory's page limit (jit_source's mem_pages): at most kMadPages, a lane's
-// granule address fits 32 bits (granule_addr)
-thread_local uint32_t g_mem_pages = 65536;
-constexpr uint32_t kMadPages = 1000;
+bool is_xfer(uint16_t op) { return op == OP_CALL || op == OP_RET; }
+bool is_branch_op(uint16_t op) {
+  return op == OP_JMP || op == OP_BR_IF || op == OP_BR_UNLESS || (op >= OP_BR_EQ && op <= OP_BR_GE_U_I);
+}
+bool ends_run(uint16_t op) { return is_xfer(op) || is_branch_op(op) || op == OP_BR_TABLE || op == OP_TAIL_CALL; }
+
+// What one jit_source call compiles for
+struct JitTarget {
+  const Program &P;
+  uint32_t glog;            // linear-memory granule = 4 << glog bytes
+  const JitCost *cost;      // metered contexts (else null)
+  // The word offsets of the extra memories in a lane's block (batch_ctx.h xinfo_h: memory k
+  // at word xinfo[2 (k - 1)]; null in dry runs) and their granule (4 << xlog bytes, KParams::xlog)
+  const std::vector<uint32_t> *xinfo;
+  uint32_t xlog;
+  uint32_t mem_pages;       // the first memory's page limit (kMadPages)
+};
+
+// The module's runs by start pc and its functions by entry pc (laid out in order of entry)
+struct RunIndex {
+  std::map<uint32_t, size_t> start;       // run start pc -> run index
+  std::map<uint32_t, uint32_t> fentry;    // entry pc -> function index
+  uint32_t ncode;
+  RunIndex(const Program &P, const std::vector<JitRun> &runs) : ncode(uint32_t(P.code.size())) {
+    for (size_t k = 0; k < runs.size(); k++) start.emplace(runs[k].pc, k);
+    for (uint32_t f = 0; f < P.funcs.size(); f++)
+      if (!P.funcs[f].imported) fentry[P.funcs[f].entry_pc] = f;
+  }
+  bool has(uint32_t pc) const { return start.count(pc) != 0; }       // a run starts at pc
+  size_t at(uint32_t pc) const { return start.find(pc)->second; }    // (has(pc)) which
+  int64_t func_of(uint32_t pc) const {                                // -1: none
+    auto it = fentry.upper_bound(pc);
+    return it == fentry.begin() ? -1 : int64_t(std::prev(it)->second);
+  }
+  uint32_t func_end(uint32_t pc) const {   // the first pc past the function that holds pc
+    auto nx = fentry.upper_bound(pc);
+    return nx == fentry.end() ? ncode : nx->first;
+  }
+};
 
 // compare ops: VOPC suffix (32-bit form; the 64-bit form appends "64" to the type)
 const char *cmp_kind(uint16_t k) {   // k: 0 EQ, 1 NE, 2 LT_S, 3 LT_U, 4 GT_S, 5 GT_U, 6 LE_S, 7 LE_U, 8 GE_S, 9 GE_U
@@ -89,6 +117,31 @@ uint16_t cmp_swap(uint16_t k) {   // a CMP b == b CMP' a
 }
 
 struct Em {
+  // Every Em comes from this constructor (a run's code, or plain text with run 0) or from
+  // one of the two factories below (`metered` is for the caller to set: only a run's own
+  // code in a metered context adds gas)
+  explicit Em(const JitTarget &tg, uint32_t run_ = 0, const std::vector<uint8_t> *nob = nullptr)
+      : t(&tg), g(tg.glog), run(run_), fb(tg.P.global_cells), prog(&tg.P),
+        nanobs(nob) {}
+  // an inlined callee's code inside this run's (jit_source): its cells `shift_` higher,
+  // `done_` counting the caller's run before it
+  Em inlined(uint32_t run_, uint32_t shift_, uint32_t done_) const {
+    Em ei(*t, run_, nanobs);
+    ei.shift = shift_;
+    ei.done = done_;
+    return ei;
+  }
+  // one stage of a run in trip mode (trip_source); nx4_: the source's counter of Lx4 labels
+  static Em trip_stage(const JitTarget &tg, uint32_t run_, const std::vector<uint8_t> *nob, uint32_t done_,
+                       const std::string &stage_end_, int *nx4_) {
+    Em e(tg, run_, nob);
+    e.trip = true;
+    e.done = done_;
+    e.stage_end = stage_end_;
+    e.nx4 = nx4_;
+    return e;
+  }
+  const JitTarget *t;
   std::string o;
   uint32_t g = 0;        // granule log
   uint32_t run = 0;      // run index (label suffix)
@@ -155,19 +208,17 @@ struct Em {
   std::string P(uint32_t c) const {
     return "v[" + std::to_string(128 + sc(c)) + ":" + std::to_string(129 + sc(c)) + "]";
   }
-  const char *v(uint32_t c) {   // (short-lived: valid until the next call)
-    static thread_local std::string s[8];
-    static thread_local int k = 0;
-    k = (k + 1) & 7;
-    s[k] = V(c);
-    return s[k].c_str();
+  std::string vs[8], ps[8];   // v() / p() results, in rotation
+  int vk = 0, pk = 0;
+  const char *v(uint32_t c) {   // (short-lived: valid until the eighth call after it)
+    vk = (vk + 1) & 7;
+    vs[vk] = V(c);
+    return vs[vk].c_str();
   }
   const char *p(uint32_t c) {
-    static thread_local std::string s[8];
-    static thread_local int k = 0;
-    k = (k + 1) & 7;
-    s[k] = P(c);
-    return s[k].c_str();
+    pk = (pk + 1) & 7;
+    ps[pk] = P(c);
+    return ps[pk].c_str();
   }
   // wait for loads in flight into any of these cells (read after load, write after load)
   void sync(std::initializer_list<uint32_t> cells) {
@@ -234,24 +285,24 @@ struct Em {
   // re-executes it from intact sources), else the temporaries R0 R1 Z0 Z1 (put128 copies
   // them). pair64: the two 64-bit halves as aligned pairs (c even) for f64 / u64 ops.
   std::string dst[4], dstp[2];
+  const char *out128[4];
   // lanewise: result word (pair) k depends only on word (pair) k of each source and is
   // written after it is read, so a source that IS the result (c..c+3 exactly) may be
   // overwritten in place
   const char *const *res128(uint32_t c, std::initializer_list<std::pair<uint32_t, uint32_t>> src,
                             bool pair64 = false, bool lanewise = false) {
     static const char *const tmp[4] = {R0, R1, Z0, Z1};
-    static thread_local const char *out[4];
     bool direct = !(pair64 && (c & 1));
     for (const auto &r : src)
       if (r.first < c + 4 && c < r.first + r.second && !(lanewise && r.first == c && r.second == 4))
         direct = false;
     for (int k = 0; k < 4; k++) {
       dst[k] = direct ? V(c + k) : "";
-      out[k] = direct ? dst[k].c_str() : tmp[k];
+      out128[k] = direct ? dst[k].c_str() : tmp[k];
     }
     dstp[0] = direct ? P(c) : RP;
     dstp[1] = direct ? P(c + 2) : ZP;
-    return out;
+    return out128;
   }
   // NaN results fixed in place (an out-of-line block, taken only when some active lane's
   // result is a NaN) to what the reference's x86 build produces: the first NaN operand,
@@ -369,6 +420,7 @@ struct Em {
   std::vector<uint32_t> inval;
   std::string stage_end;   // label: the end of the run's current stage (EXEC = its lanes)
   int nleave = 0;
+  int *nx4 = nullptr;      // (trip stages) the source's count of 16-byte window loads (labels)
   std::string trip_leave() {
     const std::string id = std::to_string(run) + "_" + std::to_string(nleave++);
     l("s_and_b64 %s, %s, exec", T2, T2);
@@ -620,10 +672,11 @@ bool emit_store(Em &e, uint16_t op, uint32_t a, uint32_t b, uint32_t imm, const 
 // No write mark: Reset rewrites the extra memories whole.
 // RP = the lane's granule 0 of memory k: s[98:99] + xinfo[2 (k - 1)] * 256 + lane * (4 << g)
 void xmem_lane_base(Em &e, uint32_t k) {
-  const uint64_t woff = g_xinfo && size_t(2 * (k - 1)) < g_xinfo->size() ? (*g_xinfo)[2 * (k - 1)] : 0;
+  const std::vector<uint32_t> *xi = e.t->xinfo;
+  const uint64_t woff = xi && size_t(2 * (k - 1)) < xi->size() ? (*xi)[2 * (k - 1)] : 0;
   e.l("v_mbcnt_lo_u32_b32 %s, -1, 0", W0);
   e.l("v_mbcnt_hi_u32_b32 %s, -1, %s", W0, W0);
-  e.l("v_lshlrev_b32_e32 %s, %u, %s", W0, 2 + g_xlog, W0);
+  e.l("v_lshlrev_b32_e32 %s, %u, %s", W0, 2 + e.t->xlog, W0);
   if (woff) {
     e.l("s_add_u32 s68, s98, 0x%x", uint32_t(woff << 8));
     e.l("s_addc_u32 s69, s99, 0x%x", uint32_t(woff >> 24));
@@ -672,9 +725,9 @@ bool emit_xmem(Em &e, const DInstr &I) {
   xmem_lane_base(e, k);
   const uint32_t nw = n >= 4 ? n / 4 : 1;   // words (or the one sub-word access)
   std::string adr[4];                       // each one's "vaddr, off[ offset:k]"
-  if (g_xlog) {   // granules of 4 << g bytes: each word's granule address in a pair of its own
+  if (e.t->xlog) {   // granules of 4 << g bytes: each word's granule address in a pair of its own
     static const char *const PR[4] = {"v[118:119]", "v[126:127]", "v[108:109]", "v[110:111]"};
-    const uint32_t g = g_xlog;
+    const uint32_t g = e.t->xlog;
     for (uint32_t q = 0; q < nw; q++) {
       std::string ea = e.V(a);
       if (imm + 4 * q) { e.l("v_add_u32_e32 %s, 0x%x, %s", Y1, imm + 4 * q, e.v(a)); ea = Y1; }
@@ -1340,215 +1393,6 @@ bool emit(Em &e, const DInstr &I) {
   return false;
 }
 
-// ---------------------------------------------------------------- scheduling
-// One wave per SIMD (64K instances fill the chip) hides no latency: a VALU instruction
-// that needs the result of the one before waits for it (measured: ~12 cycles per
-// instruction along a dependent chain against 4 for independent ones). The run's code is
-// therefore list-scheduled between barriers (anything but a VALU instruction: scalar
-// code, branches, memory, waits), on the registers each instruction names: true, anti
-// and output dependences kept, independent chains (BLAKE3's four column / diagonal G
-// functions) interleaved.
-struct SIns {
-  std::string text;
-  std::vector<int> defs, uses;
-  bool wait = false;   // a counted vmcnt wait: defs = the registers of the loads it retires
-  int est = 0;         // (wait) estimated cycle its loads are in
-  bool store = false;  // a global store: uses its address and data registers
-};
-
-void regs_of(const std::string &tok, std::vector<int> *out) {
-  // vN, v[N:M], sN, s[N:M], vcc (VGPR k -> k, SGPR k -> 1000 + k, vcc -> 2000)
-  size_t i = 0;
-  while (i < tok.size()) {
-    const char ch = tok[i];
-    const bool word_start = i == 0 || !(isalnum((unsigned char)tok[i - 1]) || tok[i - 1] == '_');
-    if (word_start && tok.compare(i, 3, "vcc") == 0) { out->push_back(2000); i += 3; continue; }
-    if (word_start && (ch == 'v' || ch == 's') && i + 1 < tok.size()) {
-      const int base = ch == 'v' ? 0 : 1000;
-      if (tok[i + 1] == '[') {
-        int lo = 0, hi = 0;
-        if (sscanf(tok.c_str() + i + 2, "%d:%d", &lo, &hi) == 2)
-          for (int r = lo; r <= hi; r++) out->push_back(base + r);
-        i = tok.find(']', i) + 1;
-        continue;
-      }
-      if (isdigit((unsigned char)tok[i + 1])) {
-        out->push_back(base + atoi(tok.c_str() + i + 1));
-        i++;
-        while (i < tok.size() && isdigit((unsigned char)tok[i])) i++;
-        continue;
-      }
-    }
-    i++;
-  }
-}
-
-bool parse_valu(const std::string &line, SIns *ins) {
-  ins->text = line;
-  if (line.compare(0, 2, "v_") != 0) return false;
-  const size_t sp = line.find(' ');
-  if (sp == std::string::npos) return false;
-  const std::string mn = line.substr(0, sp);
-  std::vector<std::string> ops;
-  for (size_t at = sp + 1; at <= line.size();) {
-    size_t cm = line.find(", ", at);
-    if (cm == std::string::npos) cm = line.size();
-    ops.push_back(line.substr(at, cm - at));
-    at = cm + 2;
-  }
-  const size_t ndef = mn.find("_co_") != std::string::npos ? 2 : 1;   // v_add_co: vdst, sdst
-  for (size_t k = 0; k < ops.size(); k++) regs_of(ops[k], k < ndef ? &ins->defs : &ins->uses);
-  return true;
-}
-
-std::string schedule(const std::string &body) {
-  std::vector<std::string> lines;
-  for (size_t at = 0; at < body.size();) {
-    const size_t nl = body.find('\n', at);
-    lines.push_back(body.substr(at, nl - at));
-    at = nl + 1;
-  }
-  std::string out;
-  std::vector<SIns> seg;
-  auto flush = [&]() {
-    const size_t n = seg.size();
-    if (n > 1) {
-      // dependences: j -> i (j earlier) with a latency in cycles
-      constexpr int kIssue = 4, kLat = 12;
-      std::vector<std::vector<std::pair<int, int>>> pred(n), succ(n);
-      std::map<int, int> last_def;
-      std::map<int, std::vector<int>> readers;
-      int last_wait = -1;
-      for (size_t i = 0; i < n; i++) {
-        std::map<int, int> dep;   // pred -> latency
-        for (int r : seg[i].uses) {
-          auto it = last_def.find(r);
-          if (it != last_def.end())
-            dep[it->second] = std::max(dep[it->second], seg[size_t(it->second)].wait ? 0 : kLat);
-        }
-        // waits and stores keep their order (the counts are issue-order counts)
-        if ((seg[i].wait || seg[i].store) && last_wait >= 0) dep[last_wait] = std::max(dep[last_wait], 0);
-        if (seg[i].wait || seg[i].store) last_wait = int(i);
-        for (int r : seg[i].defs) {
-          auto it = last_def.find(r);
-          if (it != last_def.end()) dep[it->second] = std::max(dep[it->second], 1);
-          for (int j : readers[r])
-            if (j != int(i)) dep[j] = std::max(dep[j], 1);
-        }
-        for (auto &d : dep) {
-          pred[i].push_back({d.first, d.second});
-          succ[size_t(d.first)].push_back({int(i), d.second});
-        }
-        for (int r : seg[i].uses) readers[r].push_back(int(i));
-        for (int r : seg[i].defs) { last_def[r] = int(i); readers[r].clear(); }
-      }
-      std::vector<int> height(n, 0);   // longest latency path to the segment's end
-      for (size_t i = n; i-- > 0;)
-        for (auto &s : succ[i]) height[i] = std::max(height[i], height[size_t(s.first)] + s.second);
-      std::vector<int> npred(n), at(n, 0);
-      for (size_t i = 0; i < n; i++) {
-        npred[i] = int(pred[i].size());
-        if (seg[i].wait) at[i] = seg[i].est;
-      }
-      std::vector<int> ready;
-      for (size_t i = 0; i < n; i++)
-        if (!npred[i]) ready.push_back(int(i));
-      int clock = 0;
-      while (!ready.empty()) {
-        size_t best = 0;
-        for (size_t k = 1; k < ready.size(); k++) {
-          const int a = ready[k], b = ready[best];
-          const int ta = std::max(at[size_t(a)], clock), tb = std::max(at[size_t(b)], clock);
-          if (ta < tb || (ta == tb && (height[size_t(a)] > height[size_t(b)] ||
-                                       (height[size_t(a)] == height[size_t(b)] && a < b))))
-            best = k;
-        }
-        const int i = ready[best];
-        ready.erase(ready.begin() + long(best));
-        const int t = std::max(at[size_t(i)], clock);
-        clock = seg[size_t(i)].wait ? t : t + kIssue;
-        out += seg[size_t(i)].text;
-        out += '\n';
-        for (auto &s : succ[size_t(i)]) {
-          at[size_t(s.first)] = std::max(at[size_t(s.first)], t + s.second);
-          if (--npred[size_t(s.first)] == 0) ready.push_back(s.first);
-        }
-      }
-    } else if (n == 1) {
-      out += seg[0].text;
-      out += '\n';
-    }
-    seg.clear();
-  };
-  // Counted waits float: the vector-memory operations issued so far (oldest first, the
-  // registers each load writes) tell which loads an "s_waitcnt vmcnt(N)" retires; the
-  // wait becomes an instruction of the segment that defines those registers, so their
-  // readers stay behind it and independent VALU work moves above it. A label whose
-  // arrivals may differ (anything but an inlined call's Lpa / a NaN fix's Lnr return)
-  // makes the state unknown until the next full wait, and waits then stay barriers.
-  constexpr int kLoadLat = 100, kLoadStep = 22;   // cycles: first L2-hit load, each further
-  const char *fse = getenv("WB_SCHED_STORES");   // 0: stores stay barriers (A/B aid)
-  const bool float_stores = !(fse && fse[0] == '0');
-  std::vector<std::vector<int>> vq;   // operations in flight, oldest first
-  bool known = true;
-  int retired = 0;                    // loads retired by this segment's waits so far
-  for (const auto &ln : lines) {
-    SIns ins;
-    if (parse_valu(ln, &ins)) {
-      seg.push_back(std::move(ins));
-      continue;
-    }
-    int nwait = -1;
-    if (ln.compare(0, 16, "s_waitcnt vmcnt(") == 0 && ln.find("lgkmcnt") == std::string::npos)
-      nwait = atoi(ln.c_str() + 16);
-    if (nwait >= 0 && known) {
-      SIns w;
-      w.text = ln;
-      w.wait = true;
-      while (vq.size() > size_t(nwait)) {
-        for (int r : vq.front()) w.defs.push_back(r);
-        vq.erase(vq.begin());
-        retired++;
-      }
-      w.est = kLoadLat + kLoadStep * retired;
-      seg.push_back(std::move(w));
-      continue;
-    }
-    if (ln.compare(0, 12, "global_store") == 0 && known && float_stores) {
-      // a store only reads registers: VALU work moves across it (its data and address
-      // registers' writers stay before it, later writers after it)
-      SIns st;
-      st.text = ln;
-      st.store = true;
-      const size_t sp = ln.find(' ');
-      if (sp != std::string::npos) regs_of(ln.substr(sp + 1), &st.uses);
-      seg.push_back(std::move(st));
-      vq.push_back({});
-      continue;
-    }
-    flush();
-    retired = 0;
-    out += ln;
-    out += '\n';
-    if (ln.compare(0, 11, "global_load") == 0) {
-      std::vector<int> d;
-      const size_t sp = ln.find(' '), cm = ln.find(',');
-      if (sp != std::string::npos && cm != std::string::npos) regs_of(ln.substr(sp + 1, cm - sp - 1), &d);
-      vq.push_back(d);
-    } else if (ln.compare(0, 7, "global_") == 0 || ln.compare(0, 7, "buffer_") == 0) {
-      vq.push_back({});
-    } else if (ln.find("vmcnt(0)") != std::string::npos) {
-      vq.clear();
-      known = true;
-    } else if (!ln.empty() && ln.back() == ':' && ln.compare(0, 3, "Lpa") != 0 &&
-               ln.compare(0, 3, "Lnr") != 0) {
-      known = false;
-    }
-  }
-  flush();
-  return out;
-}
-
 // cells an instruction writes (for the access groups: a write to the address cell ends
 // its group)
 void written(const DInstr &I, std::vector<uint32_t> *out) {
@@ -1614,8 +1458,7 @@ struct LoadBatch {
   std::vector<uint32_t> order;   // issue order (body indices)
 };
 
-bool load_wide(uint16_t op) { return load_wide_op(op); }
-uint32_t load_cells(uint16_t op) { return op == OP_LD128 ? 4u : load_wide(op) ? 2u : 1u; }
+uint32_t load_cells(uint16_t op) { return op == OP_LD128 ? 4u : load_wide_op(op) ? 2u : 1u; }
 
 // an operand field naming the cell (or the cell below it: a 64-bit operand's high word);
 // only the batch's issue order depends on it
@@ -1678,8 +1521,6 @@ std::vector<LoadBatch> load_batches(const Program &P, const JitRun &r, uint32_t 
   return out;
 }
 
-bool emit(Em &e, const DInstr &I);
-
 // the batch's checks (leaving before its first load), then its loads in issue order
 void emit_batch(Em &e, const Program &P, uint32_t rpc, const LoadBatch &b,
                 const std::vector<MemGroup> &G, const std::vector<int> &lead) {
@@ -1710,8 +1551,6 @@ void emit_batch(Em &e, const Program &P, uint32_t rpc, const LoadBatch &b,
 // first in program order (the interpreter resumes a run that leaves mid-way at the same
 // instruction), so the zero is never observed. Writes are taken only from instructions
 // whose destination is certain; any operand field that names the cell counts as a read.
-bool is_xfer(uint16_t op);
-bool is_branch_op(uint16_t op);
 std::vector<uint8_t> dead_zeros(const Program &P, const JitRun &r) {
   std::vector<uint8_t> dead(TC_VF_CELLS, 0), seen(TC_VF_CELLS, 0);
   for (uint32_t i = 0; i < r.len; i++) {
@@ -1892,9 +1731,8 @@ bool jit_ok(const Program &P, const DInstr &I) {
   const uint16_t op = op_of(I);
   if (const uint32_t n = mem_bytes(op))
     if (uint64_t(I.w3) + n - 1 > 0xFFFFFFFFull) return false;
-  Em e;
-  e.fb = P.global_cells;
-  e.prog = &P;
+  const JitTarget dry{P, 0, nullptr, nullptr, 0, 65536};
+  Em e(dry);
   return emit(e, I);
 }
 
@@ -1911,12 +1749,6 @@ int64_t JitCost::taken(uint32_t to, int32_t jtc) const {
 }
 
 namespace {
-
-bool is_xfer(uint16_t op) { return op == OP_CALL || op == OP_RET; }
-bool is_branch_op(uint16_t op) {
-  return op == OP_JMP || op == OP_BR_IF || op == OP_BR_UNLESS || (op >= OP_BR_EQ && op <= OP_BR_GE_U_I);
-}
-bool ends_run(uint16_t op) { return is_xfer(op) || is_branch_op(op) || op == OP_BR_TABLE || op == OP_TAIL_CALL; }
 
 
 // The compare of a branch into vcc (true = taken).
@@ -2010,56 +1842,6 @@ void long_jump(Em &e, const std::string &to, const std::string &tag) {
 // a long jump)
 void cond_jump(Em &e, const std::string &to, const std::string &tag) {
   e.l("LJCC %s %s", to.c_str(), tag.c_str());
-}
-
-std::string resolve_jumps(const std::string &body) {
-  std::vector<std::string> lines;
-  for (size_t at = 0; at < body.size();) {
-    size_t nl = body.find('\n', at);
-    if (nl == std::string::npos) nl = body.size();
-    lines.push_back(body.substr(at, nl - at));
-    at = nl + 1;
-  }
-  // an upper bound on the bytes before each line: 12 per instruction (8 + a literal),
-  // 64 per alignment
-  std::vector<uint64_t> pos(lines.size() + 1, 0);
-  std::map<std::string, size_t> lab;
-  for (size_t i = 0; i < lines.size(); i++) {
-    const std::string &ln = lines[i];
-    uint64_t b = 12;
-    if (ln.empty() || ln[0] == '.') b = ln.compare(0, 8, ".p2align") == 0 ? 64 : 0;
-    if (ln.compare(0, 5, "LJMP ") == 0 || ln.compare(0, 5, "LJCC ") == 0) b = 48;   // (the long form)
-    if (!ln.empty() && ln.back() == ':') { lab[ln.substr(0, ln.size() - 1)] = i; b = 0; }
-    pos[i + 1] = pos[i] + b;
-  }
-  std::string out;
-  out.reserve(body.size() + body.size() / 4);
-  for (size_t i = 0; i < lines.size(); i++) {
-    const std::string &ln = lines[i];
-    const bool cc = ln.compare(0, 5, "LJCC ") == 0;
-    if (ln.compare(0, 5, "LJMP ") != 0 && !cc) { out += ln; out += '\n'; continue; }
-    const size_t sp = ln.find(' ', 5);
-    const std::string to = ln.substr(5, sp - 5), tag = ln.substr(sp + 1);
-    auto it = lab.find(to);
-    const uint64_t d = it == lab.end() ? ~0ull
-                                       : (pos[it->second] > pos[i] ? pos[it->second] - pos[i]
-                                                                    : pos[i] - pos[it->second]);
-    if (d < 100000) {
-      out += (cc ? "s_cbranch_scc1 " : "s_branch ") + to + "\n";
-    } else if (cc) {
-      out += "s_cbranch_scc0 " + tag + "_n\n";
-      out += "s_getpc_b64 s[68:69]\n" + tag + ":\n";
-      out += "s_add_u32 s68, s68, " + to + " - " + tag + "\n";
-      out += "s_addc_u32 s69, s69, (" + to + " - " + tag + ") >> 32\n";
-      out += "s_setpc_b64 s[68:69]\n" + tag + "_n:\n";
-    } else {
-      out += "s_getpc_b64 s[68:69]\n" + tag + ":\n";
-      out += "s_add_u32 s68, s68, " + to + " - " + tag + "\n";
-      out += "s_addc_u32 s69, s69, (" + to + " - " + tag + ") >> 32\n";
-      out += "s_setpc_b64 s[68:69]\n";
-    }
-  }
-  return out;
 }
 
 // min over the lanes of `mask` (an SGPR pair) of VPC into SGPR `dst` (~0 when none);
@@ -2222,8 +2004,8 @@ void sched_block(Em &e, const std::string &p, const char *mask, bool depth = fal
 // hybrid (trip mode beside SIMT scheduling, jit_source): a wave whose lanes are not all at
 // one pc goes to the trips (Ltin) instead of picking a group; the trips come back here
 // once every lane is at one pc again.
-std::string simt_sched(bool hybrid, bool depth) {
-  Em e;
+std::string simt_sched(const JitTarget &t, bool hybrid, bool depth) {
+  Em e(t);
   e.l(".p2align 6");
   e.l("Lmerge:");
   e.l("v_lshrrev_b32_e64 %s, 5, s62", VPC);
@@ -2251,7 +2033,6 @@ std::string simt_sched(bool hybrid, bool depth) {
 //   br_<cmp> y, p (or p, y; p loop-invariant; an immediate form) back to the run's start
 // runs kTripScan iterations per trip in trip mode (trip_scan_stage): every lane's next
 // loads go out together, then each lane's exit iteration is found in order.
-constexpr uint32_t kTripScan = 4;   // trip mode: scan iterations per trip (trip_scan_stage)
 constexpr uint32_t kTripBatch = 4;  // trip mode: lane-test compares issued together (trip_source)
 constexpr uint32_t kTripGuard = 4;  // trip mode: a function's runs share one range test from this many
 // (mem: the memory the load reads -- 0, or k >= 1 for an XLD of a 32-bit word, whose
@@ -2348,7 +2129,8 @@ bool written_exact(const DInstr &I, std::vector<uint32_t> *out) {
 // live (non-null): plain liveness instead -- every source of a result is live when the
 // instruction runs (float compares and truncations included, their operands taken 4 cells
 // wide), and *live receives the cells live before each pc (bit sets of total_cells() + 8)
-std::vector<uint8_t> nan_observable(const Program &P, std::vector<std::vector<uint64_t>> *live = nullptr) {
+std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
+                                    std::vector<std::vector<uint64_t>> *live = nullptr) {
   const size_t n = P.code.size();
   const uint32_t nc = P.total_cells() + 8;   // (+8: 4-wide over-approximations stay in range)
   const size_t W = (nc + 63) / 64;
@@ -2532,9 +2314,9 @@ std::vector<uint8_t> nan_observable(const Program &P, std::vector<std::vector<ui
     }
   }
   if (live) *live = before;
-  // (debugging aid: WB_NANOBS_LIST=<file> writes per pc the flag and the cells observable
+  // (debugging aid: WB_NANOBS_LIST=<file>, JitKnobs::nanobs_list, writes per pc the flag and the cells observable
   // before it)
-  if (const char *lst = getenv("WB_NANOBS_LIST"))
+  if (const char *lst = kn.nanobs_list)
     if (FILE *f = fopen(lst, "w")) {
       for (size_t pc = 0; pc < n; pc++) {
         fprintf(f, "%4zu %d", pc, int(res[pc]));
@@ -2733,16 +2515,41 @@ void scan_window_fails(Em &e, const ScanLoop &sl, uint32_t U) {
   e.l("s_or_b64 %s, %s, vcc", T2, T2);
 }
 
+// (word by word: RP already set for an extra memory)
+void scan_window_words(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<std::string> &dst) {
+  for (uint32_t j = 1; j <= U; j++) {
+    e.l("v_add_u32_e32 %s, 0x%x, %s", Y0, uint32_t(int64_t(sl.off) + int64_t(sl.d) * j), e.v(sl.x));
+    if (sl.mem && !e.t->xlog) {   // (an extra memory in the word interleave)
+      e.l("v_mov_b32 %s, %s", W0, Y0);
+      e.l("v_lshlrev_b64 %s, 6, %s", XP, WP);
+      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, RP);
+    } else if (sl.mem) {       // (an extra memory in granules of 4 << xlog bytes)
+      e.l("v_lshrrev_b32_e32 %s, %u, %s", W0, 2 + e.t->xlog, Y0);
+      e.l("v_lshlrev_b64 %s, %u, %s", XP, 8 + e.t->xlog, WP);
+      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, RP);
+      e.l("v_bfe_u32 %s, %s, 0, %u", W0, Y0, 2 + e.t->xlog);
+      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, WP, XP);
+    } else if (e.g == 0) {
+      e.l("v_mov_b32 %s, %s", W0, Y0);
+      e.l("v_lshlrev_b64 %s, 6, %s", XP, WP);
+      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, MEM);
+    } else {
+      granule_addr(e, XP, Y0, MEM);
+    }
+    e.l("global_load_dword %s, %s, off", dst[j - 1].c_str(), XP);
+  }
+}
+
 // the scan window's U words into dst[0..U-1] (the window checked)
-void scan_window_words(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<std::string> &dst);
-void scan_window_loads(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<std::string> &dst) {
+void scan_window_loads(Em &e, const JitKnobs &kn, const ScanLoop &sl, uint32_t U,
+                       const std::vector<std::string> &dst) {
   if (sl.mem) xmem_lane_base(e, sl.mem);   // (RP: the lane's word 0 of memory k)
   // One 16-byte load per lane whose window lies in one granule (granules of 16 bytes or
   // more, |d| = 4, the destination registers consecutive in address order), the word by
   // word path for the others (WB_TRIP_X4=0: word by word always)
-  const uint32_t g = sl.mem ? g_xlog : e.g;
+  const uint32_t g = sl.mem ? e.t->xlog : e.g;
   int r = -1;
-  if (U == 4 && g >= 2 && (sl.d == 4 || sl.d == -4) && !(getenv("WB_TRIP_X4") && getenv("WB_TRIP_X4")[0] == '0')) {
+  if (U == 4 && g >= 2 && (sl.d == 4 || sl.d == -4) && kn.trip_x4) {
     int lo = -1;
     bool ok = true;
     for (uint32_t q = 0; q < 4 && ok; q++) {   // q-th word in address order
@@ -2754,8 +2561,7 @@ void scan_window_loads(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<
     if (ok && !(lo & 1)) r = lo;   // (VGPR tuples start at even registers)
   }
   if (r < 0) { scan_window_words(e, sl, U, dst); return; }
-  static thread_local int nx4 = 0;
-  const std::string id = std::to_string(nx4++);
+  const std::string id = std::to_string((*e.nx4)++);
   const char *base = sl.mem ? RP : MEM;
   const uint32_t lo_off = uint32_t(int64_t(sl.off) + (sl.d > 0 ? 4 : -16));
   e.l("v_add_u32_e32 %s, 0x%x, %s", Y0, lo_off, e.v(sl.x));
@@ -2782,31 +2588,6 @@ void scan_window_loads(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<
   e.l("s_mov_b64 exec, s[68:69]");
 }
 
-// (word by word: RP already set for an extra memory)
-void scan_window_words(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<std::string> &dst) {
-  for (uint32_t j = 1; j <= U; j++) {
-    e.l("v_add_u32_e32 %s, 0x%x, %s", Y0, uint32_t(int64_t(sl.off) + int64_t(sl.d) * j), e.v(sl.x));
-    if (sl.mem && !g_xlog) {   // (an extra memory in the word interleave)
-      e.l("v_mov_b32 %s, %s", W0, Y0);
-      e.l("v_lshlrev_b64 %s, 6, %s", XP, WP);
-      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, RP);
-    } else if (sl.mem) {       // (an extra memory in granules of 4 << g_xlog bytes)
-      e.l("v_lshrrev_b32_e32 %s, %u, %s", W0, 2 + g_xlog, Y0);
-      e.l("v_lshlrev_b64 %s, %u, %s", XP, 8 + g_xlog, WP);
-      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, RP);
-      e.l("v_bfe_u32 %s, %s, 0, %u", W0, Y0, 2 + g_xlog);
-      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, WP, XP);
-    } else if (e.g == 0) {
-      e.l("v_mov_b32 %s, %s", W0, Y0);
-      e.l("v_lshlrev_b64 %s, 6, %s", XP, WP);
-      e.l("v_lshl_add_u64 %s, %s, 0, %s", XP, XP, MEM);
-    } else {
-      granule_addr(e, XP, Y0, MEM);
-    }
-    e.l("global_load_dword %s, %s, off", dst[j - 1].c_str(), XP);
-  }
-}
-
 // The successor-window prefetch (trip_source): in stage A of a scan run that falls into
 // another scan run (Hoare's i-scan into its j-scan), every lane also loads the successor's
 // window at the successor's current x into pf.v[0..U-1] and records that x in pf.x (-1:
@@ -2815,7 +2596,7 @@ void scan_window_words(Em &e, const ScanLoop &sl, uint32_t U, const std::vector<
 // memory's: pf.x is invalidated by every store of the lane and at the trips' entry.
 struct ScanPrefetch { uint32_t x = 0; std::vector<std::string> v; };
 
-void trip_scan_prefetch(Em &e, const ScanLoop &succ, uint32_t U, const ScanPrefetch &pf,
+void trip_scan_prefetch(Em &e, const JitKnobs &kn, const ScanLoop &succ, uint32_t U, const ScanPrefetch &pf,
                         const std::string &L) {
   e.l("v_mov_b32 v%u, -1", pf.x);
   scan_window_fails(e, succ, U);
@@ -2823,7 +2604,7 @@ void trip_scan_prefetch(Em &e, const ScanLoop &succ, uint32_t U, const ScanPrefe
   e.l("s_andn2_b64 exec, exec, %s", T2);
   e.l("s_cbranch_execz %s_pf", L.c_str());
   e.l("v_mov_b32 v%u, %s", pf.x, e.v(succ.x));
-  scan_window_loads(e, succ, U, pf.v);
+  scan_window_loads(e, kn, succ, U, pf.v);
   e.l("%s_pf:", L.c_str());
   e.l("s_or_b64 exec, exec, s[84:85]");
 }
@@ -2838,9 +2619,7 @@ const char *scan_T(const ScanLoop &sl, uint32_t j) {
 
 // win: (stage B, branch-free form) the window's registers when every lane of the stage has
 // its window there already (LtS: the successor prefetch's), else v108.. and the v112 flag
-bool scan_bf_on() { return !(getenv("WB_TRIP_SCANBF") && getenv("WB_TRIP_SCANBF")[0] == '0'); }
-
-void trip_scan_stage(Em &e, const Program &P, const JitRun &r, const ScanLoop &sl, uint32_t U,
+void trip_scan_stage(Em &e, const JitKnobs &kn, const Program &P, const JitRun &r, const ScanLoop &sl, uint32_t U,
                      int st, bool fall_in, const std::string &L, std::pair<int, int> slot,
                      const std::vector<std::string> *win = nullptr) {
   const char *T[kTripScan];
@@ -2855,7 +2634,7 @@ void trip_scan_stage(Em &e, const Program &P, const JitRun &r, const ScanLoop &s
     e.l("s_andn2_b64 exec, exec, %s", T2);       // window lanes
     e.l("s_cbranch_execz %s_sp", L.c_str());
     e.l("v_mov_b32 v112, 1");
-    scan_window_loads(e, sl, U, std::vector<std::string>(T, T + U));
+    scan_window_loads(e, kn, sl, U, std::vector<std::string>(T, T + U));
     e.l("%s_sp:", L.c_str());
     e.l("s_mov_b64 exec, s[84:85]");
     e.l("s_cbranch_execz %s", e.stage_end.c_str());
@@ -2871,7 +2650,7 @@ void trip_scan_stage(Em &e, const Program &P, const JitRun &r, const ScanLoop &s
     e.l("s_and_b64 exec, exec, vcc");
     e.l("s_cbranch_execz %s_sb", L.c_str());
   }
-  if (scan_bf_on()) {
+  if (kn.trip_scanbf) {
     // Branch-free (WB_TRIP_SCANBF=0: the iteration-by-iteration form below): each lane's
     // exit iteration E (U + 1: none) and the word it ended on, from the last iteration to
     // the first; then x += d * min(E, U), the count min(E, U) * (cnt + tcnt) less the
@@ -2966,47 +2745,43 @@ bool ret_prefetch_run(const Program &P, const JitRun &r) {
   return op_of(f) == OP_POST_CALL && (f.w1 & 0xFFFFu) > P.global_cells && op_of(l) == OP_RET;
 }
 
-// hybrid: only the trips' code (Ltin, the trip loop, the runs' stages, the exits), for
-// jit_source's SIMT code object, whose Lsched sends diverged waves to Ltin; a trip after
-// which every lane is at one pc goes back to Lsched (SIMT scheduling, direct run-to-run
-// jumps) -- converged phases (C3's fill and checksum loops; modules like mt19937 whose
-// addresses merely look divergent to the static analysis) run without trips.
-std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint32_t glog, bool hybrid) {
-  std::map<uint32_t, size_t> start;
-  for (size_t k = 0; k < runs.size(); k++) start[runs[k].pc] = k;
-  auto in_region = [&](uint32_t pc) { return start.count(pc) != 0; };
+namespace {
+
+// What trip_source decides about the runs before it writes any code
+struct TripPlan {
+  std::map<int64_t, std::vector<uint32_t>> ret_out;   // function -> return pcs outside the runs
+  std::vector<uint32_t> ind_out;                      // the pcs after every call_indirect outside them
+  std::vector<std::pair<int, int>> slot_of;           // run -> its load-cache VGPRs {address, value} (-1: none)
+  bool mad_on = false;                                // granule_addr's constant in v255 (Em::madk)
+  std::vector<uint32_t> split;                        // run -> its stage A's length (trip_split; 0: none)
+  uint32_t scan_k = 0;                                // scan iterations per trip (below 2: no scan stages)
+  std::vector<ScanLoop> scans;
+  std::vector<uint8_t> is_scan;
+  // the load cache's consumers: runs with a stage A of 32-bit loads at scan slots only
+  std::vector<std::map<uint32_t, std::pair<uint32_t, uint32_t>>> fwd;   // (Em::fwd)
+  std::vector<uint8_t> fwd_ok;
+  // the successor-window prefetch: pf_to[q] = the scan run scan q falls into, pf_from[s] = q
+  std::vector<int> pf_to, pf_from;
+  std::vector<ScanPrefetch> pfr;
+  std::vector<uint32_t> inval;                        // what a store invalidates (Em::inval)
+  uint32_t G = 1;                                     // lane tests per batch
+  std::vector<std::vector<uint32_t>> gblk;            // block start -> the last runs of its guard blocks (outer first)
+  // stage-B batches: run k's test reads PREG[k - bfirst[k]]; a stage-B run k recomputes
+  // the masks of runs k+1 .. blast[k]
+  std::vector<uint32_t> bfirst, blast;
+  uint32_t trip_cost = 256;                           // what a trip takes off the core's budget
+};
+
+TripPlan plan_trips(const JitTarget &t, const JitKnobs &kn, const RunIndex &ix, const std::vector<JitRun> &runs) {
+  const Program &P = t.P;
+  const uint32_t nr = uint32_t(runs.size());
+  TripPlan tp;
   // the pcs a return of function f can land on: after each direct call of f and after
   // every call_indirect
-  std::map<uint32_t, uint32_t> fentry;
-  for (uint32_t f = 0; f < P.funcs.size(); f++)
-    if (!P.funcs[f].imported) fentry[P.funcs[f].entry_pc] = f;
-  auto func_of = [&](uint32_t pc) -> int64_t {
-    auto it = fentry.upper_bound(pc);
-    return it == fentry.begin() ? -1 : int64_t(std::prev(it)->second);
-  };
-  std::map<int64_t, std::vector<uint32_t>> ret_out;   // function -> return pcs outside the runs
-  std::vector<uint32_t> ind_out;
   for (uint32_t pc = 0; pc + 1 < P.code.size(); pc++) {
     const uint16_t o = op_of(P.code[pc]);
-    if (o == OP_CALL && !in_region(pc + 1)) ret_out[func_of(P.code[pc].w3)].push_back(pc + 1);
-    if (o == OP_CALL_INDIRECT && !in_region(pc + 1)) ind_out.push_back(pc + 1);
-  }
-  std::string body;
-  if (!hybrid)
-    body += "s_getpc_b64 s[6:7]\nLpt:\ns_add_u32 s6, s6, Ltab - Lpt\ns_addc_u32 s7, s7, 0\n"
-            "s_mov_b32 %0, s6\ns_mov_b32 %1, s7\n"
-            "s_getpc_b64 s[8:9]\nLpe:\ns_add_u32 s8, s8, Lend - Lpe\ns_addc_u32 s9, s9, 0\n"
-            "s_setpc_b64 s[8:9]\n";
-  Em h;   // entry stubs, the trip loop and its exits
-  // a run's entry (its TInstr): the group's lanes record their pc and count; then every
-  // lane's place is sorted out (OUTSIDE: not at a run start) and the trips begin
-  // (hybrid: the runs' TInstrs enter their SIMT code; Lsched enters the trips)
-  for (size_t k = 0; k < runs.size() && !hybrid; k++) {
-    h.l(".p2align 6");   // (jit_load expects 64-byte aligned run addresses)
-    h.l("Lb%zu:", k);
-    h.l("v_lshrrev_b32_e64 %s, 5, s62", VPC);
-    flush(h);
-    long_jump(h, "Ltin", "Ltiq" + std::to_string(k));
+    if (o == OP_CALL && !ix.has(pc + 1)) tp.ret_out[ix.func_of(P.code[pc].w3)].push_back(pc + 1);
+    if (o == OP_CALL_INDIRECT && !ix.has(pc + 1)) tp.ind_out.push_back(pc + 1);
   }
   // ---- the load cache (WB_TRIP_FWD=0 turns it off). A lane's scan that ends leaves the
   // word it ended on and that word's address in VGPRs above the frame (a slot per scan
@@ -3016,63 +2791,51 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
   // this same trip, its loads as moves -- instead of waiting for the next trip's stage A.
   // A slot is invalid (-1) from the trips' entry (Ltin: code outside the trips may have
   // stored), from its scan's stage A, and after any store of the lane (emit_store).
-  const bool fwd_on = !(getenv("WB_TRIP_FWD") && getenv("WB_TRIP_FWD")[0] == '0');
-  std::vector<std::pair<int, int>> slot_of(runs.size(), {-1, -1});
+  tp.slot_of.assign(runs.size(), {-1, -1});
   // granule_addr's constant (Em::madk) in v255 when the first memory stays below kMadPages
   // (WB_TRIP_MAD=0: the 64-bit form); the slots below it
-  const bool mad_on = g_mem_pages <= kMadPages && P.has_mem && 128 + 2 * P.total_cells() + 16 < 255 &&
-                      !(getenv("WB_TRIP_MAD") && getenv("WB_TRIP_MAD")[0] == '0');
-  const uint32_t top = mad_on ? 254 : 255;
+  tp.mad_on = t.mem_pages <= kMadPages && P.has_mem && 128 + 2 * P.total_cells() + 16 < 255 && kn.trip_mad;
+  const uint32_t top = tp.mad_on ? 254 : 255;
   std::vector<uint32_t> slot_regs;   // address VGPRs
   {
     uint32_t ns = 0;
     for (size_t k = 0; k < runs.size(); k++) {
       ScanLoop sl;
-      if (!fwd_on || !scan_loop_of(P, runs[k], &sl)) continue;
+      if (!kn.trip_fwd || !scan_loop_of(P, runs[k], &sl)) continue;
       const int a = int(top) - 2 * int(ns), v = a - 1;
       // (above the frame, above what inlined callees may use of it, never the frame's)
       if (uint32_t(v) < 128 + 2 * P.total_cells() + 16) break;
-      slot_of[k] = {a, v};
+      tp.slot_of[k] = {a, v};
       slot_regs.push_back(uint32_t(a));
       ns++;
     }
   }
-  std::string ooa, oob;   // the runs' stage code, out of line
-  std::vector<uint32_t> split(runs.size());
-  const uint32_t nr = uint32_t(runs.size());
-  // (A/B and debugging aids: WB_TRIP_SPLIT=0 runs every run whole in stage B;
-  // WB_JIT_SCHED=0 keeps program order)
-  const bool split_on = !(getenv("WB_TRIP_SPLIT") && getenv("WB_TRIP_SPLIT")[0] == '0');
-  const bool sched_on = !(getenv("WB_JIT_SCHED") && getenv("WB_JIT_SCHED")[0] == '0');
-  const bool nob_on = !(getenv("WB_NANOBS") && getenv("WB_NANOBS")[0] == '0');
-  const std::vector<uint8_t> nob = nob_on ? nan_observable(P) : std::vector<uint8_t>();
-  const bool ret_pf_on = !(getenv("WB_RET_PF") && getenv("WB_RET_PF")[0] == '0');
-  const bool brt_on = !(getenv("WB_BRT_THREAD") && getenv("WB_BRT_THREAD")[0] == '0');
-  for (uint32_t k = 0; k < nr && split_on; k++) {
+  // (A/B and debugging aid: WB_TRIP_SPLIT=0 runs every run whole in stage B)
+  tp.split.assign(nr, 0);
+  for (uint32_t k = 0; k < nr && kn.trip_split; k++) {
     const JitRun &r = runs[k];
     const uint16_t lop = op_of(P.code[r.pc + r.len - 1]);
-    split[k] = trip_split(P, r, ends_run(lop) ? r.len - 1 : r.len);
+    tp.split[k] = trip_split(P, r, ends_run(lop) ? r.len - 1 : r.len);
   }
   // Scan loops (scan_loop_of: `x += d; y = load(x + off); br y CMP p` back to the run's
   // start) run kTripScan iterations per trip: stage A checks the whole window of kTripScan
   // addresses once per lane and loads them all; stage B finds each lane's exit iteration
   // in order. A lane whose window fails the check (near its memory's end) takes the plain
   // one-iteration path, which meets a failing access exactly. WB_TRIP_SCAN=0 turns it off.
-  const char *tse = getenv("WB_TRIP_SCAN");
-  const uint32_t scan_k = tse ? std::min<uint32_t>(uint32_t(atoi(tse)), kTripScan) : kTripScan;
-  std::vector<ScanLoop> scans(nr);
-  std::vector<uint8_t> is_scan(nr, 0);
-  for (uint32_t k = 0; k < nr && scan_k >= 2; k++)
-    is_scan[k] = split[k] == 2 && scan_loop_of(P, runs[k], &scans[k]);
+  tp.scan_k = kn.trip_scan;
+  tp.scans.assign(nr, ScanLoop());
+  tp.is_scan.assign(nr, 0);
+  for (uint32_t k = 0; k < nr && tp.scan_k >= 2; k++)
+    tp.is_scan[k] = tp.split[k] == 2 && scan_loop_of(P, runs[k], &tp.scans[k]);
   for (uint32_t k = 0; k < nr; k++)
-    if (!is_scan[k]) slot_of[k] = {-1, -1};   // (its cache slot is never set: unused)
+    if (!tp.is_scan[k]) tp.slot_of[k] = {-1, -1};   // (its cache slot is never set: unused)
   // the load cache's consumers: runs with a stage A of 32-bit loads at scan slots only
-  std::vector<std::map<uint32_t, std::pair<uint32_t, uint32_t>>> fwd(nr);
-  std::vector<uint8_t> fwd_ok(nr, 0);
+  tp.fwd.assign(nr, {});
+  tp.fwd_ok.assign(nr, 0);
   for (uint32_t k = 0; k < nr && !slot_regs.empty(); k++) {
-    if (!split[k] || is_scan[k]) continue;
+    if (!tp.split[k] || tp.is_scan[k]) continue;
     bool ok = true, any = false;
-    for (uint32_t i = 0; i < split[k] && ok; i++) {
+    for (uint32_t i = 0; i < tp.split[k] && ok; i++) {
       const DInstr &I = P.code[runs[k].pc + i];
       const uint16_t op = op_of(I);
       if (!mem_bytes(op) && !xmop(I)) continue;
@@ -3081,117 +2844,41 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
       if (op != OP_LD32 && !xl) break;
       const uint32_t mk = xl ? (I.w1 >> 16) : 0;   // (the cache holds its scan's memory's words)
       for (uint32_t q = 0; q < nr; q++)
-        if (is_scan[q] && slot_of[q].first >= 0 && scans[q].mem == mk && scans[q].x == (I.w1 & 0xFFFFu) &&
-            scans[q].off == I.w3) {
-          fwd[k][runs[k].pc + i] = {uint32_t(slot_of[q].first), uint32_t(slot_of[q].second)};
+        if (tp.is_scan[q] && tp.slot_of[q].first >= 0 && tp.scans[q].mem == mk && tp.scans[q].x == (I.w1 & 0xFFFFu) &&
+            tp.scans[q].off == I.w3) {
+          tp.fwd[k][runs[k].pc + i] = {uint32_t(tp.slot_of[q].first), uint32_t(tp.slot_of[q].second)};
           ok = any = true;
           break;
         }
     }
-    fwd_ok[k] = ok && any;
+    tp.fwd_ok[k] = ok && any;
   }
   // the successor-window prefetch (trip_scan_prefetch; WB_TRIP_PF=0 turns it off):
   // pf_to[q] = the scan run scan q falls into, pf_from[s] = q
-  const bool pf_on = !(getenv("WB_TRIP_PF") && getenv("WB_TRIP_PF")[0] == '0');
-  std::vector<int> pf_to(nr, -1), pf_from(nr, -1);
-  std::vector<ScanPrefetch> pfr(nr);
-  std::vector<uint32_t> inval = slot_regs;   // (what a store invalidates: Em::inval)
+  tp.pf_to.assign(nr, -1);
+  tp.pf_from.assign(nr, -1);
+  tp.pfr.assign(nr, ScanPrefetch());
+  tp.inval = slot_regs;
   {
     uint32_t next = top - 2 * uint32_t(slot_regs.size());   // below the cache slots
-    for (uint32_t q = 0; q < nr && pf_on && scan_k >= 2; q++) {
-      if (!is_scan[q] || !start.count(runs[q].pc + 3)) continue;
-      const uint32_t s = uint32_t(start[runs[q].pc + 3]);
-      if (s == q || !is_scan[s] || pf_from[s] >= 0) continue;
+    for (uint32_t q = 0; q < nr && kn.trip_pf && tp.scan_k >= 2; q++) {
+      if (!tp.is_scan[q] || !ix.has(runs[q].pc + 3)) continue;
+      const uint32_t s = uint32_t(ix.at(runs[q].pc + 3));
+      if (s == q || !tp.is_scan[s] || tp.pf_from[s] >= 0) continue;
       // (x in `next`, the window below it from an even register in address order: one
       // 16-byte load can fill it, scan_window_loads)
-      const uint32_t lo = (next - scan_k) & ~1u;
+      const uint32_t lo = (next - tp.scan_k) & ~1u;
       if (lo < 128 + 2 * P.total_cells() + 16) break;   // (as the slots)
-      pfr[q].x = next;
-      for (uint32_t j = 0; j < scan_k; j++)
-        pfr[q].v.push_back("v" + std::to_string(scans[s].d < 0 ? lo + scan_k - 1 - j : lo + j));
+      tp.pfr[q].x = next;
+      for (uint32_t j = 0; j < tp.scan_k; j++)
+        tp.pfr[q].v.push_back("v" + std::to_string(tp.scans[s].d < 0 ? lo + tp.scan_k - 1 - j : lo + j));
       next = lo - 1;
-      pf_to[q] = int(s);
-      pf_from[s] = int(q);
-      inval.push_back(pfr[q].x);
+      tp.pf_to[q] = int(s);
+      tp.pf_from[s] = int(q);
+      tp.inval.push_back(tp.pfr[q].x);
     }
   }
-  h.l(".p2align 6");
-  h.l("Ltin:");
-  h.l("s_waitcnt lgkmcnt(0)");   // (a handler's bank-B prefetch must land: the batches use s[86:91])
-  h.l("s_mov_b64 exec, s[96:97]");
-  for (uint32_t r : inval) h.l("v_mov_b32 v%u, -1", r);
-  if (mad_on) h.l("v_mov_b32 v255, 0x%x", 63u << (2 + glog));
-  h.l("s_mov_b64 s[76:77], s[96:97]");
-  h.l("s_mov_b64 s[78:79], 0");
-  for (const auto &r : runs) {
-    h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", r.pc, VPC);
-    h.l("s_andn2_b64 s[76:77], s[76:77], vcc");
-  }
-  // TPC for the next trip: the pc of every lane in the runs, -1 outside
-  h.l("Ltp:");
-  h.l("s_mov_b64 exec, s[96:97]");
-  h.l("v_cndmask_b32_e64 %s, %s, -1, s[76:77]", TPC, VPC);
-  // ---- the trip (EXEC = ALL between the runs)
-  h.l("Ltrip:");
-  // Batched lane tests (WB_TRIP_BATCH=0 turns them off): a run's test is a VALU compare
-  // whose mask a scalar branch reads, and that VALU -> SALU -> branch chain costs ~48
-  // cycles against ~20 for the branch alone (tools/ubench/lat.hip). So the compares of up
-  // to kTripBatch consecutive tests go out back to back into their own masks (s[80:81],
-  // s[86:91]: free between the runs; the trips start after every SMEM load has landed),
-  // and the tests then read them. A stage-A run moves no other run's lanes (it only takes
-  // its own out of TPC), so its batch stays valid; a stage-B run may move lanes onto later
-  // runs (VPC), so it recomputes the rest of its batch before it returns (stage end), and a
-  // run with its own LtF / LtS tests ends a batch.
-  const bool batch_on = !(getenv("WB_TRIP_BATCH") && getenv("WB_TRIP_BATCH")[0] == '0');
-  // Inline stages (WB_TRIP_INLINE=0 turns it off): a run's stage code sits in the test
-  // chain right after its test, which branches past it when no lane is there -- a stage
-  // that takes lanes costs no taken branch (out of line it costs two: there and back), one
-  // that takes none costs one. Taken branches are what the trips' scalar stream waits on (a
-  // taken branch refetches: ~20 cycles, tools/ubench/lat.hip); C3 1 MiB +6% with stage B
-  // inline (profiles/r06zb_bench_c3_*).
-  const bool inline_on = !(getenv("WB_TRIP_INLINE") && getenv("WB_TRIP_INLINE")[0] == '0');
-  const bool smask_on = !(getenv("WB_TRIP_SMASK") && getenv("WB_TRIP_SMASK")[0] == '0');
-  const bool cmpbr_on = !(getenv("WB_TRIP_CMPBR") && getenv("WB_TRIP_CMPBR")[0] == '0');
-  // dst = (v == pc) per lane; VOP3 takes no literal, so a pc past the inline constants goes
-  // through s68 / s69 (alternating: the compare has read one before the next is written)
-  auto vcmp64 = [](Em &x, const char *dst, uint32_t pc, const char *v, uint32_t j) {
-    if (pc <= 64) {
-      x.l("v_cmp_eq_u32_e64 %s, %u, %s", dst, pc, v);
-    } else {
-      x.l("s_mov_b32 s%u, 0x%x", 68 + (j & 1), pc);
-      x.l("v_cmp_eq_u32_e64 %s, s%u, %s", dst, 68 + (j & 1), v);
-    }
-  };
-  static const char *const PREG[kTripBatch] = {"s[80:81]", "s[86:87]", "s[88:89]", "s[90:91]"};
-  const uint32_t G = batch_on ? kTripBatch : 1;
-  {
-    std::vector<uint32_t> a;
-    for (uint32_t k = 0; k < nr; k++)
-      if (split[k]) a.push_back(k);
-    for (size_t b = 0; b < a.size(); b += G) {
-      const size_t e = std::min(a.size(), b + G);
-      if (batch_on)
-        for (size_t j = b; j < e; j++) vcmp64(h, PREG[j - b], runs[a[j]].pc, TPC, uint32_t(j - b));
-      for (size_t j = b; j < e; j++) {
-        if (batch_on) {
-          h.l("s_and_b64 s[74:75], %s, exec", PREG[j - b]);
-        } else {
-          h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[a[j]].pc, TPC);
-          h.l("s_and_b64 s[74:75], vcc, exec");
-        }
-        h.l("@@LtA%u@@", a[j]);   // (the test's branch and, inline, the stage-A code: below)
-        h.l("LtAr%u:", a[j]);
-      }
-    }
-  }
-  h.l("s_waitcnt vmcnt(0)");
-  // Forward chaining (WB_TRIP_CHAIN=0 turns it off): a run without a stage A takes every
-  // lane now at its start -- the lanes that began the trip there and those an earlier
-  // run of this trip moved there -- except the lanes waiting outside the trips (escapes
-  // included). A run with a stage A takes only the lanes that began the trip there.
-  const bool chain = !(getenv("WB_TRIP_CHAIN") && getenv("WB_TRIP_CHAIN")[0] == '0');
-  // stage-B batches: run k's test reads PREG[k - bfirst[k]]; a stage-B run k recomputes
-  // the masks of runs k+1 .. blast[k] (trip_source's stage code, below)
+  tp.G = kn.trip_batch ? kTripBatch : 1;
   // Guards (WB_TRIP_GUARD=0 turns them off): a block of consecutive runs is skipped after
   // one range test while no lane's VPC lies in its pc range (none of its tests could take
   // lanes then). The blocks: (1) the runs of one function -- C3's `sort` (fill and checksum
@@ -3204,9 +2891,9 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
   // (VPC alone decides: a lane that a stage-B test takes by its TPC began the trip at that
   // run's pc and is still there -- a stage-A run moves none of its lanes but the ones that
   // leave, which take TPC -1, and no other run's test takes it.)
-  const bool guard_on = batch_on && !(getenv("WB_TRIP_GUARD") && getenv("WB_TRIP_GUARD")[0] == '0');
+  const bool guard_on = kn.trip_batch && kn.trip_guard;
   std::vector<int64_t> fn_of(nr);
-  for (uint32_t k = 0; k < nr; k++) fn_of[k] = func_of(runs[k].pc);
+  for (uint32_t k = 0; k < nr; k++) fn_of[k] = ix.func_of(runs[k].pc);
   std::vector<uint8_t> in_loop(nr, 0);   // some backward branch spans the run's start
   for (uint32_t pc = 0; pc < P.code.size(); pc++) {
     const DInstr &I = P.code[pc];
@@ -3220,11 +2907,11 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
       if (t <= pc)
         for (uint32_t k = 0; k < nr; k++) in_loop[k] |= runs[k].pc >= t && runs[k].pc <= pc;
   }
-  std::vector<std::vector<uint32_t>> gblk(nr);   // block start -> the last runs of its blocks (outer first)
+  tp.gblk.assign(nr, {});   // block start -> the last runs of its blocks (outer first)
   std::vector<uint8_t> cut(nr + 1, 0);            // a block's edge lies before run k
   auto add_block = [&](uint32_t k, uint32_t e) {
     if (e + 1 - k < kTripGuard) return;
-    gblk[k].push_back(e);
+    tp.gblk[k].push_back(e);
     cut[k] = cut[e + 1] = 1;
   };
   for (uint32_t k = 0; k < nr && guard_on;) {
@@ -3240,20 +2927,152 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
     }
     k = e + 1;
   }
-  std::vector<uint32_t> bfirst(nr, 0), blast(nr, 0);
+  tp.bfirst.assign(nr, 0);
+  tp.blast.assign(nr, 0);
   for (uint32_t k = 0; k < nr;) {
     uint32_t e = k;
-    while (e + 1 < nr && e + 1 - k < G && !fwd_ok[e] && pf_from[e] < 0 && !cut[e + 1]) e++;
-    for (uint32_t j = k; j <= e; j++) { bfirst[j] = k; blast[j] = e; }
+    while (e + 1 < nr && e + 1 - k < tp.G && !tp.fwd_ok[e] && tp.pf_from[e] < 0 && !cut[e + 1]) e++;
+    for (uint32_t j = k; j <= e; j++) { tp.bfirst[j] = k; tp.blast[j] = e; }
     k = e + 1;
   }
-  auto b_cmp = [&](Em &x, uint32_t k) {   // run k's test mask into its batch register
-    vcmp64(x, PREG[k - bfirst[k]], runs[k].pc, chain && !split[k] ? VPC : TPC, k - bfirst[k]);
-  };
+  // (>= what one lane can retire in a trip: one run, or with chaining every run once)
+  tp.trip_cost = 256;
+  uint32_t chained = 0;
+  for (uint32_t k = 0; k < nr; k++) {
+    const JitRun &r = runs[k];
+    tp.trip_cost = std::max(tp.trip_cost, r.cnt);
+    chained += (tp.fwd_ok[k] ? 2 : 1) * (r.cnt + 64);   // (+ a taken branch's correction)
+    if (tp.is_scan[k]) {
+      const uint32_t sc = tp.scan_k * uint32_t(std::max<int32_t>(
+                                       0, int32_t(r.cnt) + int16_t(P.code[r.pc + 2].w2 >> 16))) + r.cnt;
+      tp.trip_cost = std::max<uint32_t>(tp.trip_cost, sc);
+      if (tp.pf_from[k] >= 0) chained += sc + 64;   // (LtS: a whole window in the same trip)
+    }
+  }
+  if (kn.trip_chain) tp.trip_cost = std::max(tp.trip_cost, chained + (uint32_t)kTripScan * 64u);
+  return tp;
+}
+
+// dst = (v == pc) per lane; VOP3 takes no literal, so a pc past the inline constants goes
+// through s68 / s69 (alternating: the compare has read one before the next is written)
+void vcmp64(Em &x, const char *dst, uint32_t pc, const char *v, uint32_t j) {
+  if (pc <= 64) {
+    x.l("v_cmp_eq_u32_e64 %s, %u, %s", dst, pc, v);
+  } else {
+    x.l("s_mov_b32 s%u, 0x%x", 68 + (j & 1), pc);
+    x.l("v_cmp_eq_u32_e64 %s, s%u, %s", dst, 68 + (j & 1), v);
+  }
+}
+const char *const PREG[kTripBatch] = {"s[80:81]", "s[86:87]", "s[88:89]", "s[90:91]"};
+
+// The emission half: `h` holds the entry stubs, the trip loop with the runs' tests (and the
+// stages placed inline) and the exits; ooa / oob the stages out of line
+struct TripEmit {
+  const JitTarget &t;
+  const JitKnobs &kn;
+  const RunIndex &ix;
+  const std::vector<JitRun> &runs;
+  const std::vector<uint8_t> &nob;
+  const bool hybrid;
+  const TripPlan &tp;
+  const Program &P;
+  const uint32_t nr;
+  Em h;
+  std::string ooa, oob;
+  int nx4 = 0;   // (Em::nx4)
+
+  TripEmit(const JitTarget &t_, const JitKnobs &kn_, const RunIndex &ix_, const std::vector<JitRun> &runs_,
+           const std::vector<uint8_t> &nob_, bool hybrid_, const TripPlan &tp_)
+      : t(t_), kn(kn_), ix(ix_), runs(runs_), nob(nob_), hybrid(hybrid_), tp(tp_), P(t_.P),
+        nr(uint32_t(runs_.size())), h(t_) {}
+
+  void b_cmp(Em &x, uint32_t k) {   // run k's test mask into its batch register
+    vcmp64(x, PREG[k - tp.bfirst[k]], runs[k].pc, kn.trip_chain && !tp.split[k] ? VPC : TPC, k - tp.bfirst[k]);
+  }
+  void entry_stubs();
+  void trip_entry();
+  void tests_a();
+  void tests_b();
+  void after_trip();
+  bool run_stages(uint32_t k);
+};
+
+void TripEmit::entry_stubs() {
+  // a run's entry (its TInstr): the group's lanes record their pc and count; then every
+  // lane's place is sorted out (OUTSIDE: not at a run start) and the trips begin
+  // (hybrid: the runs' TInstrs enter their SIMT code; Lsched enters the trips)
+  for (size_t k = 0; k < runs.size() && !hybrid; k++) {
+    h.l(".p2align 6");   // (jit_load expects 64-byte aligned run addresses)
+    h.l("Lb%zu:", k);
+    h.l("v_lshrrev_b32_e64 %s, 5, s62", VPC);
+    flush(h);
+    long_jump(h, "Ltin", "Ltiq" + std::to_string(k));
+  }
+}
+
+void TripEmit::trip_entry() {
+  h.l(".p2align 6");
+  h.l("Ltin:");
+  h.l("s_waitcnt lgkmcnt(0)");   // (a handler's bank-B prefetch must land: the batches use s[86:91])
+  h.l("s_mov_b64 exec, s[96:97]");
+  for (uint32_t r : tp.inval) h.l("v_mov_b32 v%u, -1", r);
+  if (tp.mad_on) h.l("v_mov_b32 v255, 0x%x", 63u << (2 + t.glog));
+  h.l("s_mov_b64 s[76:77], s[96:97]");
+  h.l("s_mov_b64 s[78:79], 0");
+  for (const auto &r : runs) {
+    h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", r.pc, VPC);
+    h.l("s_andn2_b64 s[76:77], s[76:77], vcc");
+  }
+  // TPC for the next trip: the pc of every lane in the runs, -1 outside
+  h.l("Ltp:");
+  h.l("s_mov_b64 exec, s[96:97]");
+  h.l("v_cndmask_b32_e64 %s, %s, -1, s[76:77]", TPC, VPC);
+  // ---- the trip (EXEC = ALL between the runs)
+  h.l("Ltrip:");
+}
+
+void TripEmit::tests_a() {
+  // Batched lane tests (WB_TRIP_BATCH=0 turns them off): a run's test is a VALU compare
+  // whose mask a scalar branch reads, and that VALU -> SALU -> branch chain costs ~48
+  // cycles against ~20 for the branch alone (tools/ubench/lat.hip). So the compares of up
+  // to kTripBatch consecutive tests go out back to back into their own masks (s[80:81],
+  // s[86:91]: free between the runs; the trips start after every SMEM load has landed),
+  // and the tests then read them. A stage-A run moves no other run's lanes (it only takes
+  // its own out of TPC), so its batch stays valid; a stage-B run may move lanes onto later
+  // runs (VPC), so it recomputes the rest of its batch before it returns (stage end), and a
+  // run with its own LtF / LtS tests ends a batch.
+  std::vector<uint32_t> a;
+  for (uint32_t k = 0; k < nr; k++)
+    if (tp.split[k]) a.push_back(k);
+  for (size_t b = 0; b < a.size(); b += tp.G) {
+    const size_t e = std::min(a.size(), b + tp.G);
+    if (kn.trip_batch)
+      for (size_t j = b; j < e; j++) vcmp64(h, PREG[j - b], runs[a[j]].pc, TPC, uint32_t(j - b));
+    for (size_t j = b; j < e; j++) {
+      if (kn.trip_batch) {
+        h.l("s_and_b64 s[74:75], %s, exec", PREG[j - b]);
+      } else {
+        h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[a[j]].pc, TPC);
+        h.l("s_and_b64 s[74:75], vcc, exec");
+      }
+      h.l("@@LtA%u@@", a[j]);   // (the test's branch and, inline, the stage-A code: below)
+      h.l("LtAr%u:", a[j]);
+    }
+  }
+  h.l("s_waitcnt vmcnt(0)");
+}
+
+void TripEmit::tests_b() {
+  // Forward chaining (WB_TRIP_CHAIN=0 turns it off): a run without a stage A takes every
+  // lane now at its start -- the lanes that began the trip there and those an earlier
+  // run of this trip moved there -- except the lanes waiting outside the trips (escapes
+  // included). A run with a stage A takes only the lanes that began the trip there.
+  // stage-B batches: run k's test reads PREG[k - bfirst[k]]; a stage-B run k recomputes
+  // the masks of runs k+1 .. blast[k] (trip_source's stage code, below)
   std::vector<std::pair<uint32_t, uint32_t>> gopen;   // (label id, last run) of blocks still open
   uint32_t nguard = 0;
   for (uint32_t k = 0; k < nr; k++) {
-    for (uint32_t e : gblk[k]) {   // lo <= VPC <= hi (VPC - lo <= hi - lo), else past the block
+    for (uint32_t e : tp.gblk[k]) {   // lo <= VPC <= hi (VPC - lo <= hi - lo), else past the block
       const uint32_t lo = runs[k].pc, hi = runs[e].pc;
       if (lo) {
         h.l("v_subrev_u32_e32 %s, 0x%x, %s", X0, lo, VPC);
@@ -3264,12 +3083,12 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
       h.l("s_cbranch_vccz Lg%u", nguard);
       gopen.push_back({nguard++, e});
     }
-    if (batch_on && bfirst[k] == k)
-      for (uint32_t j = k; j <= blast[k]; j++) b_cmp(h, j);
-    if (batch_on) {
-      if (chain && !split[k]) h.l("s_andn2_b64 s[74:75], %s, s[76:77]", PREG[k - bfirst[k]]);
-      else h.l("s_and_b64 s[74:75], %s, exec", PREG[k - bfirst[k]]);
-    } else if (chain && !split[k]) {
+    if (kn.trip_batch && tp.bfirst[k] == k)
+      for (uint32_t j = k; j <= tp.blast[k]; j++) b_cmp(h, j);
+    if (kn.trip_batch) {
+      if (kn.trip_chain && !tp.split[k]) h.l("s_andn2_b64 s[74:75], %s, s[76:77]", PREG[k - tp.bfirst[k]]);
+      else h.l("s_and_b64 s[74:75], %s, exec", PREG[k - tp.bfirst[k]]);
+    } else if (kn.trip_chain && !tp.split[k]) {
       h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[k].pc, VPC);
       h.l("s_andn2_b64 s[74:75], vcc, s[76:77]");
     } else {
@@ -3278,7 +3097,7 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
     }
     h.l("@@LtB%u@@", k);   // (the test's branch and, inline, the stage-B code: below)
     h.l("LtBr%u:", k);
-    if (fwd_ok[k]) {   // the lanes that arrived this trip (not at its start there): LtF
+    if (tp.fwd_ok[k]) {   // the lanes that arrived this trip (not at its start there): LtF
       h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[k].pc, VPC);
       h.l("s_andn2_b64 s[74:75], vcc, s[76:77]");
       h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[k].pc, TPC);
@@ -3286,7 +3105,7 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
       h.l("@@LtF%u@@", k);
       h.l("LtFr%u:", k);
     }
-    if (pf_from[k] >= 0) {   // the lanes its prefetching scan moved here this trip: LtS
+    if (tp.pf_from[k] >= 0) {   // the lanes its prefetching scan moved here this trip: LtS
       h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[k].pc, VPC);
       h.l("s_andn2_b64 s[74:75], vcc, s[76:77]");
       h.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", runs[k].pc, TPC);
@@ -3299,6 +3118,9 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
       gopen.pop_back();
     }
   }
+}
+
+void TripEmit::after_trip() {
   // ---- after the trip: go on while more lanes are in the runs than outside them (Ltnc;
   // none in the runs implies more outside than in, since ALL is not empty). The common
   // case -- every lane in the runs, at more than one pc -- falls through to the budget and
@@ -3314,32 +3136,15 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
   // (`profiles/r06zl_*`, `r06zo_*`): a wave whose last lanes stand at one pc no longer
   // leaves the trips for SIMT scheduling and re-enters them at the next split, trip
   // after trip (each entry re-marks the lanes outside the runs, one compare per run).
-  const bool conv_every = getenv("WB_TRIP_CONV1") && getenv("WB_TRIP_CONV1")[0] == '1';
-  const char *cpe = getenv("WB_TRIP_CONVP");
-  const uint32_t conv_log = cpe ? std::min(8u, std::max(1u, uint32_t(atoi(cpe)))) : 4u;
-  if (hybrid && !conv_every) {
-    h.l("s_add_u32 s65, s65, 0x%x", 1u << (32 - conv_log));
+  if (hybrid && !kn.trip_conv1) {
+    h.l("s_add_u32 s65, s65, 0x%x", 1u << (32 - kn.trip_convp));
     h.l("s_cbranch_scc1 Ltck");
   } else if (hybrid) {
     h.l("s_branch Ltck");
   }
   h.l("Ltbud:");
-  // (>= what one lane can retire in a trip: one run, or with chaining every run once)
-  uint32_t trip_cost = 256, chained = 0;
-  for (uint32_t k = 0; k < nr; k++) {
-    const JitRun &r = runs[k];
-    trip_cost = std::max(trip_cost, r.cnt);
-    chained += (fwd_ok[k] ? 2 : 1) * (r.cnt + 64);   // (+ a taken branch's correction)
-    if (is_scan[k]) {
-      const uint32_t sc = scan_k * uint32_t(std::max<int32_t>(
-                                       0, int32_t(r.cnt) + int16_t(P.code[r.pc + 2].w2 >> 16))) + r.cnt;
-      trip_cost = std::max<uint32_t>(trip_cost, sc);
-      if (pf_from[k] >= 0) chained += sc + 64;   // (LtS: a whole window in the same trip)
-    }
-  }
-  if (chain) trip_cost = std::max(trip_cost, chained + (uint32_t)kTripScan * 64u);
   // (no borrow: go on -- a budget that reaches 0 exactly runs one more trip)
-  h.l("s_sub_u32 s64, s64, 0x%x", trip_cost);
+  h.l("s_sub_u32 s64, s64, 0x%x", tp.trip_cost);
   h.l("s_cbranch_scc0 Ltp");
   // budget spent: back to the kernel with no group (reason 1)
   h.l("s_mov_b32 s64, 0");
@@ -3365,13 +3170,11 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
   // 1.79 (1) -> 1.83 (2) -> 1.86 (3) -> 1.91 (4) -> 2.03e12 (6) per step, C3 and mt
   // unchanged: `profiles/r06zu_*`, `r06zv_*`). Lanes outside are never stranded: a budget
   // exit hands the wave back to the kernel's scheduler, which picks among every lane.
-  const char *ose = getenv("WB_TRIP_OUTSH");
-  const int out_sh = ose ? std::max(0, std::min(6, atoi(ose))) : 6;
   h.l("Ltnc:");
   h.l("s_andn2_b64 s[80:81], s[96:97], s[76:77]");
   h.l("s_bcnt1_i32_b64 s68, s[80:81]");
   h.l("s_bcnt1_i32_b64 s69, s[76:77]");
-  if (out_sh) h.l("s_lshl_b32 s68, s68, %d", out_sh);
+  if (kn.trip_outsh) h.l("s_lshl_b32 s68, s68, %d", kn.trip_outsh);
   h.l("s_cmp_gt_u32 s69, s68");
   h.l("s_cbranch_scc0 Ltbud");
   // ---- leaving the trips: escapes first (the C++ step executes their instruction: xh),
@@ -3399,384 +3202,414 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
   h.l("Ltq:");
   h.l("s_mov_b32 s65, 0");   // (the trip count of Ltck)
   sched_block(h, "Ltq", "s[76:77]");
-  // ---- the runs' stages
-  for (uint32_t k = 0; k < nr; k++) {
-    const JitRun &r = runs[k];
-    const DInstr &last = P.code[r.pc + r.len - 1];
-    const uint16_t lop = op_of(last);
-    const uint32_t nbody = ends_run(lop) ? r.len - 1 : r.len;
-    std::vector<int> lead;
-    const std::vector<MemGroup> groups = jit_groups(P, r, &lead);
-    // Groups a stage need not test (MemGroup::checked): every access of the group a 32-bit
-    // access at a (cell, offset) whose 32-bit access these lanes already passed the test
-    // for, with the cell unwritten since the run's start -- in the load cache's stage (LtF)
-    // the cached addresses (the scan windows that set them were tested), in stage B of a
-    // run with a stage A the stage-A accesses (C3's swap stores at the words its stage A
-    // loaded). WB_TRIP_FWDCHK=0 keeps every test.
-    const bool skip_on = !(getenv("WB_TRIP_FWDCHK") && getenv("WB_TRIP_FWDCHK")[0] == '0');
-    auto mark_checked = [&](std::vector<MemGroup> &gs, const std::vector<std::pair<uint32_t, uint32_t>> &ok,
-                            uint32_t from) {
-      std::vector<uint8_t> good(gs.size(), 1), written_c(TC_VF_CELLS + 8, 0);
-      int cur = -1;
-      std::vector<uint32_t> w;
-      for (uint32_t i = 0; i < r.len; i++) {
-        const DInstr &I = P.code[r.pc + i];
-        const uint16_t op = op_of(I);
-        if (lead[i] >= 0) cur = lead[i];
-        if (const uint32_t n = mem_bytes(op)) {
-          const uint32_t a = I.w1 & 0xFFFFu;
-          const bool hit = std::find(ok.begin(), ok.end(), std::make_pair(a, I.w3)) != ok.end();
-          if (cur >= 0 && (i < from || n != 4 || !hit || a >= written_c.size() || written_c[a]))
-            good[size_t(cur)] = 0;
-        } else if (xmop(I)) {
-          cur = -1;
+}
+
+// the stages of run k (placed in `h` after their tests, or out of line)
+bool TripEmit::run_stages(uint32_t k) {
+  const JitRun &r = runs[k];
+  const DInstr &last = P.code[r.pc + r.len - 1];
+  const uint16_t lop = op_of(last);
+  const uint32_t nbody = ends_run(lop) ? r.len - 1 : r.len;
+  std::vector<int> lead;
+  const std::vector<MemGroup> groups = jit_groups(P, r, &lead);
+  // Groups a stage need not test (MemGroup::checked): every access of the group a 32-bit
+  // access at a (cell, offset) whose 32-bit access these lanes already passed the test
+  // for, with the cell unwritten since the run's start -- in the load cache's stage (LtF)
+  // the cached addresses (the scan windows that set them were tested), in stage B of a
+  // run with a stage A the stage-A accesses (C3's swap stores at the words its stage A
+  // loaded). WB_TRIP_FWDCHK=0 keeps every test.
+  auto mark_checked = [&](std::vector<MemGroup> &gs, const std::vector<std::pair<uint32_t, uint32_t>> &ok,
+                          uint32_t from) {
+    std::vector<uint8_t> good(gs.size(), 1), written_c(TC_VF_CELLS + 8, 0);
+    int cur = -1;
+    std::vector<uint32_t> w;
+    for (uint32_t i = 0; i < r.len; i++) {
+      const DInstr &I = P.code[r.pc + i];
+      const uint16_t op = op_of(I);
+      if (lead[i] >= 0) cur = lead[i];
+      if (const uint32_t n = mem_bytes(op)) {
+        const uint32_t a = I.w1 & 0xFFFFu;
+        const bool hit = std::find(ok.begin(), ok.end(), std::make_pair(a, I.w3)) != ok.end();
+        if (cur >= 0 && (i < from || n != 4 || !hit || a >= written_c.size() || written_c[a]))
+          good[size_t(cur)] = 0;
+      } else if (xmop(I)) {
+        cur = -1;
+      }
+      written(I, &w);
+      for (uint32_t x : w)
+        if (x < written_c.size()) written_c[x] = 1;
+    }
+    for (size_t q = 0; q < gs.size(); q++) gs[q].checked = good[q] != 0;
+  };
+  std::vector<MemGroup> groups_f = groups, groups_b = groups;
+  if (kn.trip_fwdchk && tp.fwd_ok[k]) {
+    std::vector<std::pair<uint32_t, uint32_t>> ok;
+    for (const auto &f : tp.fwd[k]) ok.push_back({P.code[f.first].w1 & 0xFFFFu, P.code[f.first].w3});
+    mark_checked(groups_f, ok, 0);
+  }
+  if (kn.trip_fwdchk && tp.split[k] && !tp.is_scan[k]) {
+    std::vector<std::pair<uint32_t, uint32_t>> ok;
+    for (uint32_t i = 0; i < tp.split[k]; i++) {
+      const DInstr &I = P.code[r.pc + i];
+      if (mem_bytes(op_of(I)) == 4) ok.push_back({I.w1 & 0xFFFFu, I.w3});
+    }
+    mark_checked(groups_b, ok, tp.split[k]);
+  }
+  uint32_t done = 0, done_a = 0;
+  // st 0: stage A, 1: stage B, 2: the whole run for the lanes the load cache serves (LtF),
+  // 3: stage B for the lanes whose window a prefetching scan loaded this trip (LtS)
+  static const char *const stage_name[4] = {"LtA", "LtB", "LtF", "LtS"};
+  for (int st = 0; st < 4; st++) {
+    bool salu_moved = false;   // (the transfer joined its moved lanes to the batch: join_batch)
+    if (st == 0 && !tp.split[k]) continue;
+    if (st == 2 && !tp.fwd_ok[k]) continue;
+    if (st == 3 && tp.pf_from[k] < 0) continue;
+    const int sb = st == 3 ? 1 : st;   // (the stage the code is)
+    const std::string L = stage_name[st] + std::to_string(k);
+    // (labels apart from the SIMT runs')
+    Em e = Em::trip_stage(t, (hybrid ? 8 * nr : 0) + k + uint32_t(st) * nr, nob.empty() ? nullptr : &nob,
+                          st == 2 ? 0 : st == 3 ? done_a : done, L + "e", &nx4);
+    if (tp.mad_on) e.madk = "v255";
+    e.inval = tp.inval;
+    if (st == 2) e.fwd = tp.fwd[k];
+    if (kn.ret_pf && ret_prefetch_run(P, r)) {   // (POST_CALL in stage A: RET reads v113 in B)
+      e.ret_pf = true;
+      e.ret_pf_done = sb == 1 && tp.split[k] > 0;
+    }
+    e.l(".p2align 2");
+    e.l("%s:", L.c_str());
+    e.l("s_mov_b64 exec, s[74:75]");
+    if (st == 0 && tp.pf_to[k] >= 0) trip_scan_prefetch(e, kn, tp.scans[size_t(tp.pf_to[k])], tp.scan_k, tp.pfr[k], L);
+    if (st == 3) {   // the lanes still at the prefetched x: the window as if loaded in stage A
+      const ScanPrefetch &pf = tp.pfr[size_t(tp.pf_from[k])];
+      e.l("v_cmp_eq_u32_e32 vcc, v%u, %s", pf.x, e.v(tp.scans[k].x));
+      e.l("s_and_b64 exec, exec, vcc");
+      e.l("s_cbranch_execz %s", e.stage_end.c_str());
+      if (!kn.trip_scanbf) {   // (the branch-free stage B reads the prefetch registers)
+        for (uint32_t j = 0; j < tp.scan_k; j++) e.l("v_mov_b32 %s, %s", scan_T(tp.scans[k], j), pf.v[j].c_str());
+        e.l("v_mov_b32 v112, 1");
+      }
+    }
+    if (st == 2) {   // the lanes whose every cached word is at its load's address
+      // (the effective address is 33 bits: a lane whose x + offset carries, or lands on
+      // 0xFFFFFFFF -- the invalid slots' mark, never a 4-byte load in bounds -- takes
+      // the plain path, which traps it)
+      for (const auto &f : tp.fwd[k]) {
+        const DInstr &I = P.code[f.first];
+        if (I.w3) {
+          e.l("v_add_co_u32_e32 %s, vcc, 0x%x, %s", Y0, I.w3, e.v(I.w1 & 0xFFFFu));
+          e.l("s_andn2_b64 exec, exec, vcc");
+        } else {
+          e.l("v_mov_b32 %s, %s", Y0, e.v(I.w1 & 0xFFFFu));
         }
-        written(I, &w);
-        for (uint32_t x : w)
-          if (x < written_c.size()) written_c[x] = 1;
-      }
-      for (size_t q = 0; q < gs.size(); q++) gs[q].checked = good[q] != 0;
-    };
-    std::vector<MemGroup> groups_f = groups, groups_b = groups;
-    if (skip_on && fwd_ok[k]) {
-      std::vector<std::pair<uint32_t, uint32_t>> ok;
-      for (const auto &f : fwd[k]) ok.push_back({P.code[f.first].w1 & 0xFFFFu, P.code[f.first].w3});
-      mark_checked(groups_f, ok, 0);
-    }
-    if (skip_on && split[k] && !is_scan[k]) {
-      std::vector<std::pair<uint32_t, uint32_t>> ok;
-      for (uint32_t i = 0; i < split[k]; i++) {
-        const DInstr &I = P.code[r.pc + i];
-        if (mem_bytes(op_of(I)) == 4) ok.push_back({I.w1 & 0xFFFFu, I.w3});
-      }
-      mark_checked(groups_b, ok, split[k]);
-    }
-    uint32_t done = 0, done_a = 0;
-    // st 0: stage A, 1: stage B, 2: the whole run for the lanes the load cache serves (LtF),
-    // 3: stage B for the lanes whose window a prefetching scan loaded this trip (LtS)
-    static const char *const stage_name[4] = {"LtA", "LtB", "LtF", "LtS"};
-    for (int st = 0; st < 4; st++) {
-      bool salu_moved = false;   // (the transfer joined its moved lanes to the batch: join_batch)
-      if (st == 0 && !split[k]) continue;
-      if (st == 2 && !fwd_ok[k]) continue;
-      if (st == 3 && pf_from[k] < 0) continue;
-      const int sb = st == 3 ? 1 : st;   // (the stage the code is)
-      Em e;
-      e.trip = true;
-      if (mad_on) e.madk = "v255";
-      e.inval = inval;
-      if (st == 2) e.fwd = fwd[k];
-      if (!nob.empty()) e.nanobs = &nob;
-      if (ret_pf_on && ret_prefetch_run(P, r)) {   // (POST_CALL in stage A: RET reads v113 in B)
-        e.ret_pf = true;
-        e.ret_pf_done = sb == 1 && split[k] > 0;
-      }
-      e.g = glog;
-      e.fb = P.global_cells;
-      e.prog = &P;
-      e.run = (hybrid ? 8 * nr : 0) + k + uint32_t(st) * nr;   // (labels apart from the SIMT runs')
-      e.done = st == 2 ? 0 : st == 3 ? done_a : done;
-      const std::string L = stage_name[st] + std::to_string(k);
-      e.stage_end = L + "e";
-      e.l(".p2align 2");
-      e.l("%s:", L.c_str());
-      e.l("s_mov_b64 exec, s[74:75]");
-      if (st == 0 && pf_to[k] >= 0) trip_scan_prefetch(e, scans[size_t(pf_to[k])], scan_k, pfr[k], L);
-      if (st == 3) {   // the lanes still at the prefetched x: the window as if loaded in stage A
-        const ScanPrefetch &pf = pfr[size_t(pf_from[k])];
-        e.l("v_cmp_eq_u32_e32 vcc, v%u, %s", pf.x, e.v(scans[k].x));
+        e.l("v_cmp_ne_u32_e32 vcc, -1, %s", Y0);
         e.l("s_and_b64 exec, exec, vcc");
-        e.l("s_cbranch_execz %s", e.stage_end.c_str());
-        if (!scan_bf_on()) {   // (the branch-free stage B reads the prefetch registers)
-          for (uint32_t j = 0; j < scan_k; j++) e.l("v_mov_b32 %s, %s", scan_T(scans[k], j), pf.v[j].c_str());
-          e.l("v_mov_b32 v112, 1");
+        e.l("v_cmp_eq_u32_e32 vcc, v%u, %s", f.second.first, Y0);
+        e.l("s_and_b64 exec, exec, vcc");
+      }
+      e.l("s_cbranch_execz %s", e.stage_end.c_str());
+    }
+    if (tp.is_scan[k])
+      trip_scan_stage(e, kn, P, r, tp.scans[k], tp.scan_k, sb, ix.has(r.pc + 3), L, tp.slot_of[k],
+                      st == 3 && kn.trip_scanbf ? &tp.pfr[size_t(tp.pf_from[k])].v : nullptr);
+    const size_t at = e.o.size();
+    const uint32_t i0 = sb == 1 ? tp.split[k] : 0, i1 = st == 0 ? tp.split[k] : nbody;
+    for (uint32_t i = i0; i < i1; i++) {
+      const DInstr &I = P.code[r.pc + i];
+      e.pc = r.pc + i;
+      e.group = lead[i] >= 0 ? &(st == 2 ? groups_f : st == 1 ? groups_b : groups)[size_t(lead[i])] : nullptr;
+      if (!emit(e, I)) return false;
+      e.done += (I.w0 >> 16) & 0xFFu;
+    }
+    if (st < 2) done = e.done;
+    if (st == 0) done_a = e.done;
+    if (st >= 1) {
+      // (loads in flight land first: the transfer reads cells -- a branch's operands, a
+      // call's spill, a return's results)
+      e.drain();
+      // the transfer, per lane: VPC = where each lane goes on, VCNT += what the run
+      // retired (with a taken branch's count correction)
+      const uint32_t fall = r.pc + r.len;
+      const uint32_t tgt = (lop == OP_CALL || is_branch_op(lop)) ? last.w3 : 0;
+      e.pc = r.pc + r.len - 1;
+      e.group = nullptr;
+      auto out_if = [&](const char *m) { e.l("s_or_b64 s[76:77], s[76:77], %s", m); };
+      auto add_cnt = [&](int64_t c) { if (c) e.l("v_add_u32_e32 %s, 0x%x, %s", VCNT, uint32_t(c), VCNT); };
+      // Lanes moved onto a later run of this run's test batch join that run's batch mask
+      // by scalar ops on the mask that moved them (`m` is this run's EXEC, or VCC / ~VCC
+      // under it: a "vcc" / "~vcc" in its place), instead of a compare the next test would
+      // wait on (VALU -> SALU, ~28 cycles: tools/ubench/lat.hip). WB_TRIP_SMASK=0: compares.
+      auto join_batch = [&](uint32_t to, const char *m) {
+        if (st != 1 || !kn.trip_batch || !kn.trip_smask || tp.is_scan[k]) return;   // (a scan's stage moves lanes itself)
+        for (uint32_t j = k + 1; j <= tp.blast[k]; j++) {
+          if (runs[j].pc != to || tp.split[j] || !kn.trip_chain) continue;
+          const char *pr = PREG[j - tp.bfirst[j]];
+          if (m[0] == 'e') {   // ("exec")
+            e.l("s_or_b64 %s, %s, exec", pr, pr);
+          } else {
+            e.l(m[0] == '~' ? "s_andn2_b64 s[68:69], exec, vcc" : "s_and_b64 s[68:69], vcc, exec");
+            e.l("s_or_b64 %s, %s, s[68:69]", pr, pr);
+          }
         }
-      }
-      if (st == 2) {   // the lanes whose every cached word is at its load's address
-        // (the effective address is 33 bits: a lane whose x + offset carries, or lands on
-        // 0xFFFFFFFF -- the invalid slots' mark, never a 4-byte load in bounds -- takes
-        // the plain path, which traps it)
-        for (const auto &f : fwd[k]) {
-          const DInstr &I = P.code[f.first];
-          if (I.w3) {
-            e.l("v_add_co_u32_e32 %s, vcc, 0x%x, %s", Y0, I.w3, e.v(I.w1 & 0xFFFFu));
-            e.l("s_andn2_b64 exec, exec, vcc");
-          } else {
-            e.l("v_mov_b32 %s, %s", Y0, e.v(I.w1 & 0xFFFFu));
-          }
-          e.l("v_cmp_ne_u32_e32 vcc, -1, %s", Y0);
-          e.l("s_and_b64 exec, exec, vcc");
-          e.l("v_cmp_eq_u32_e32 vcc, v%u, %s", f.second.first, Y0);
-          e.l("s_and_b64 exec, exec, vcc");
+      };
+      // the run at pc when it is one br_table (a JMP onto it takes the table: WB_BRT_THREAD)
+      auto brt_thread = [&](uint32_t pc) -> int {
+        if (!kn.brt_thread || !ix.has(pc)) return -1;
+        const size_t q = ix.at(pc);
+        return runs[q].len == 1 && op_of(P.code[pc]) == OP_BR_TABLE ? int(q) : -1;
+      };
+      // the lanes a br_table sends out of the runs (Y0 = their targets)
+      auto br_table_outs = [&](const DInstr &B) {
+        std::vector<uint32_t> seen;
+        for (uint32_t q = 0; q <= (B.w1 >> 16); q++) {
+          const uint32_t t = P.brtab[2 * (B.w3 + q)];
+          if (ix.has(t) || std::find(seen.begin(), seen.end(), t) != seen.end()) continue;
+          seen.push_back(t);
+          e.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", t, Y0);
+          e.l("s_and_b64 s[68:69], vcc, exec");
+          out_if("s[68:69]");
         }
-        e.l("s_cbranch_execz %s", e.stage_end.c_str());
-      }
-      if (is_scan[k])
-        trip_scan_stage(e, P, r, scans[k], scan_k, sb, in_region(r.pc + 3), L, slot_of[k],
-                        st == 3 && scan_bf_on() ? &pfr[size_t(pf_from[k])].v : nullptr);
-      const size_t at = e.o.size();
-      const uint32_t i0 = sb == 1 ? split[k] : 0, i1 = st == 0 ? split[k] : nbody;
-      for (uint32_t i = i0; i < i1; i++) {
-        const DInstr &I = P.code[r.pc + i];
-        e.pc = r.pc + i;
-        e.group = lead[i] >= 0 ? &(st == 2 ? groups_f : st == 1 ? groups_b : groups)[size_t(lead[i])] : nullptr;
-        if (!emit(e, I)) return "";
-        e.done += (I.w0 >> 16) & 0xFFu;
-      }
-      if (st < 2) done = e.done;
-      if (st == 0) done_a = e.done;
-      if (st >= 1) {
-        // (loads in flight land first: the transfer reads cells -- a branch's operands, a
-        // call's spill, a return's results)
-        e.drain();
-        // the transfer, per lane: VPC = where each lane goes on, VCNT += what the run
-        // retired (with a taken branch's count correction)
-        const uint32_t fall = r.pc + r.len;
-        const uint32_t tgt = (lop == OP_CALL || is_branch_op(lop)) ? last.w3 : 0;
-        e.pc = r.pc + r.len - 1;
-        e.group = nullptr;
-        auto out_if = [&](const char *m) { e.l("s_or_b64 s[76:77], s[76:77], %s", m); };
-        auto add_cnt = [&](int64_t c) { if (c) e.l("v_add_u32_e32 %s, 0x%x, %s", VCNT, uint32_t(c), VCNT); };
-        // Lanes moved onto a later run of this run's test batch join that run's batch mask
-        // by scalar ops on the mask that moved them (`m` is this run's EXEC, or VCC / ~VCC
-        // under it: a "vcc" / "~vcc" in its place), instead of a compare the next test would
-        // wait on (VALU -> SALU, ~28 cycles: tools/ubench/lat.hip). WB_TRIP_SMASK=0: compares.
-        auto join_batch = [&](uint32_t to, const char *m) {
-          if (st != 1 || !batch_on || !smask_on || is_scan[k]) return;   // (a scan's stage moves lanes itself)
-          for (uint32_t j = k + 1; j <= blast[k]; j++) {
-            if (runs[j].pc != to || split[j] || !chain) continue;
-            const char *pr = PREG[j - bfirst[j]];
-            if (m[0] == 'e') {   // ("exec")
-              e.l("s_or_b64 %s, %s, exec", pr, pr);
-            } else {
-              e.l(m[0] == '~' ? "s_andn2_b64 s[68:69], exec, vcc" : "s_and_b64 s[68:69], vcc, exec");
-              e.l("s_or_b64 %s, %s, s[68:69]", pr, pr);
-            }
-          }
-        };
-        // the run at pc when it is one br_table (a JMP onto it takes the table: WB_BRT_THREAD)
-        auto brt_thread = [&](uint32_t pc) -> int {
-          if (!brt_on || !start.count(pc)) return -1;
-          const size_t q = start[pc];
-          return runs[q].len == 1 && op_of(P.code[pc]) == OP_BR_TABLE ? int(q) : -1;
-        };
-        // the lanes a br_table sends out of the runs (Y0 = their targets)
-        auto br_table_outs = [&](const DInstr &B) {
-          std::vector<uint32_t> seen;
-          for (uint32_t q = 0; q <= (B.w1 >> 16); q++) {
-            const uint32_t t = P.brtab[2 * (B.w3 + q)];
-            if (in_region(t) || std::find(seen.begin(), seen.end(), t) != seen.end()) continue;
-            seen.push_back(t);
-            e.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", t, Y0);
-            e.l("s_and_b64 s[68:69], vcc, exec");
-            out_if("s[68:69]");
-          }
-        };
-        if (is_branch_op(lop) && lop != OP_JMP) {
-          const int32_t tcnt = int32_t(int16_t(last.w2 >> 16));
-          // A br_if / br_unless on the cell the run's last instruction set from VCC (a
-          // compare: `v_cndmask cell, 0, 1, vcc` its last line, only waits after it) reads
-          // VCC itself -- no compare of the cell again; br_unless then selects the other
-          // way round (inv: VCC = not taken). WB_TRIP_CMPBR=0 compares again.
-          bool inv = false, reuse = false;
-          if ((lop == OP_BR_IF || lop == OP_BR_UNLESS) && cmpbr_on) {
-            size_t end = e.o.size();
-            while (end >= 2) {
-              const size_t b0 = e.o.rfind('\n', end - 2);
-              const size_t st0 = b0 == std::string::npos ? 0 : b0 + 1;
-              const std::string ln = e.o.substr(st0, end - st0);
-              if (ln.compare(0, 9, "s_waitcnt") == 0 || ln == "\n") { end = st0; continue; }
-              reuse = ln == "v_cndmask_b32_e64 " + std::string(e.v(last.w1 & 0xFFFFu)) + ", 0, 1, vcc\n";
-              break;
-            }
-          }
-          if (!reuse) branch_cond(e, last);   // vcc = taken
-          inv = reuse && lop == OP_BR_UNLESS;
-          // (VOP3 selects take inline constants, -16..64: the pcs and corrections of small
-          // modules need no moves)
-          auto inl = [](int64_t v) { return v >= -16 && v <= 64; };
-          std::string f = std::to_string(fall), t = std::to_string(tgt);
-          if (!inl(fall)) { e.l("v_mov_b32 %s, 0x%x", X0, fall); f = X0; }
-          if (!inl(tgt)) { e.l("v_mov_b32 %s, 0x%x", X1, tgt); t = X1; }
-          if (inv) std::swap(f, t);
-          e.l("v_cndmask_b32_e64 %s, %s, %s, vcc", VPC, f.c_str(), t.c_str());
-          if (tcnt) {
-            if (inl(tcnt)) {
-              if (inv) e.l("v_cndmask_b32_e64 %s, %d, 0, vcc", X0, tcnt);
-              else e.l("v_cndmask_b32_e64 %s, 0, %d, vcc", X0, tcnt);
-            } else {
-              e.l("v_mov_b32 %s, 0x%x", X1, uint32_t(tcnt));
-              if (inv) e.l("v_cndmask_b32_e64 %s, %s, 0, vcc", X0, X1);
-              else e.l("v_cndmask_b32_e32 %s, 0, %s, vcc", X0, X1);
-            }
-            if (r.cnt && inl(r.cnt)) {   // (the run's count in the same add)
-              e.l("v_add3_u32 %s, %s, %s, %u", VCNT, VCNT, X0, r.cnt);
-            } else {
-              e.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, X0);
-              add_cnt(r.cnt);
-            }
-          } else {
-            add_cnt(r.cnt);
-          }
-          const char *taken_m = inv ? "s_andn2_b64 s[68:69], exec, vcc" : "s_and_b64 s[68:69], vcc, exec";
-          const char *fall_m = inv ? "s_and_b64 s[68:69], vcc, exec" : "s_andn2_b64 s[68:69], exec, vcc";
-          if (!in_region(tgt)) { e.l("%s", taken_m); out_if("s[68:69]"); }
-          if (!in_region(fall)) { e.l("%s", fall_m); out_if("s[68:69]"); }
-          if (tgt == fall) {
-            join_batch(tgt, "exec");
-          } else {
-            join_batch(tgt, inv ? "~vcc" : "vcc");
-            join_batch(fall, inv ? "vcc" : "~vcc");
-          }
-          salu_moved = true;
-        } else if (lop == OP_JMP && brt_thread(tgt) >= 0) {
-          // a jump onto a run that is one br_table (C4's `br $machine` back to its state
-          // dispatch): the table's choice made here, so that a lane whose entry lies ahead
-          // in the run order goes on in this trip; a state set to a constant in this run
-          // picks its entry at compile time. Counts: this run's, the jump's taken
-          // correction, the br_table run's and its entry's correction.
-          const DInstr &B = P.code[tgt];
-          const uint32_t ba = B.w1 & 0xFFFFu, nb = B.w1 >> 16;
-          add_cnt(int64_t(r.cnt) + int16_t(last.w2 >> 16) + runs[size_t(brt_thread(tgt))].cnt);
-          int64_t kc = -1;   // the state cell's constant, if this run sets it last
-          for (uint32_t i = nbody; i-- > 0;) {
-            const DInstr &I = P.code[r.pc + i];
-            std::vector<uint32_t> w;
-            written(I, &w);
-            if (std::find(w.begin(), w.end(), ba) == w.end()) continue;
-            if (op_of(I) == OP_CONST32 && (I.w2 & 0xFFFFu) == ba) kc = I.w3;
+      };
+      if (is_branch_op(lop) && lop != OP_JMP) {
+        const int32_t tcnt = int32_t(int16_t(last.w2 >> 16));
+        // A br_if / br_unless on the cell the run's last instruction set from VCC (a
+        // compare: `v_cndmask cell, 0, 1, vcc` its last line, only waits after it) reads
+        // VCC itself -- no compare of the cell again; br_unless then selects the other
+        // way round (inv: VCC = not taken). WB_TRIP_CMPBR=0 compares again.
+        bool inv = false, reuse = false;
+        if ((lop == OP_BR_IF || lop == OP_BR_UNLESS) && kn.trip_cmpbr) {
+          size_t end = e.o.size();
+          while (end >= 2) {
+            const size_t b0 = e.o.rfind('\n', end - 2);
+            const size_t st0 = b0 == std::string::npos ? 0 : b0 + 1;
+            const std::string ln = e.o.substr(st0, end - st0);
+            if (ln.compare(0, 9, "s_waitcnt") == 0 || ln == "\n") { end = st0; continue; }
+            reuse = ln == "v_cndmask_b32_e64 " + std::string(e.v(last.w1 & 0xFFFFu)) + ", 0, 1, vcc\n";
             break;
           }
-          if (kc >= 0) {
-            const uint32_t q = std::min<uint32_t>(uint32_t(kc), nb);
-            const uint32_t t = P.brtab[2 * (B.w3 + q)];
-            e.l("v_mov_b32 %s, 0x%x", VPC, t);
-            add_cnt(int32_t(P.brtab[2 * (B.w3 + q) + 1]));
-            if (!in_region(t)) out_if("exec");
-            join_batch(t, "exec");
-            salu_moved = true;
+        }
+        if (!reuse) branch_cond(e, last);   // vcc = taken
+        inv = reuse && lop == OP_BR_UNLESS;
+        // (VOP3 selects take inline constants, -16..64: the pcs and corrections of small
+        // modules need no moves)
+        auto inl = [](int64_t v) { return v >= -16 && v <= 64; };
+        std::string f = std::to_string(fall), t = std::to_string(tgt);
+        if (!inl(fall)) { e.l("v_mov_b32 %s, 0x%x", X0, fall); f = X0; }
+        if (!inl(tgt)) { e.l("v_mov_b32 %s, 0x%x", X1, tgt); t = X1; }
+        if (inv) std::swap(f, t);
+        e.l("v_cndmask_b32_e64 %s, %s, %s, vcc", VPC, f.c_str(), t.c_str());
+        if (tcnt) {
+          if (inl(tcnt)) {
+            if (inv) e.l("v_cndmask_b32_e64 %s, %d, 0, vcc", X0, tcnt);
+            else e.l("v_cndmask_b32_e64 %s, 0, %d, vcc", X0, tcnt);
           } else {
-            emit_br_table(e, B);
-            e.l("v_mov_b32 %s, %s", VPC, Y0);
-            e.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, Y1);
-            br_table_outs(B);
+            e.l("v_mov_b32 %s, 0x%x", X1, uint32_t(tcnt));
+            if (inv) e.l("v_cndmask_b32_e64 %s, %s, 0, vcc", X0, X1);
+            else e.l("v_cndmask_b32_e32 %s, 0, %s, vcc", X0, X1);
           }
-        } else if (lop == OP_JMP) {
-          e.l("v_mov_b32 %s, 0x%x", VPC, tgt);
-          add_cnt(int64_t(r.cnt) + int16_t(last.w2 >> 16));
-          if (!in_region(tgt)) out_if("exec");
+          if (r.cnt && inl(r.cnt)) {   // (the run's count in the same add)
+            e.l("v_add3_u32 %s, %s, %s, %u", VCNT, VCNT, X0, r.cnt);
+          } else {
+            e.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, X0);
+            add_cnt(r.cnt);
+          }
+        } else {
+          add_cnt(r.cnt);
+        }
+        const char *taken_m = inv ? "s_andn2_b64 s[68:69], exec, vcc" : "s_and_b64 s[68:69], vcc, exec";
+        const char *fall_m = inv ? "s_and_b64 s[68:69], vcc, exec" : "s_andn2_b64 s[68:69], exec, vcc";
+        if (!ix.has(tgt)) { e.l("%s", taken_m); out_if("s[68:69]"); }
+        if (!ix.has(fall)) { e.l("%s", fall_m); out_if("s[68:69]"); }
+        if (tgt == fall) {
           join_batch(tgt, "exec");
+        } else {
+          join_batch(tgt, inv ? "~vcc" : "vcc");
+          join_batch(fall, inv ? "vcc" : "~vcc");
+        }
+        salu_moved = true;
+      } else if (lop == OP_JMP && brt_thread(tgt) >= 0) {
+        // a jump onto a run that is one br_table (C4's `br $machine` back to its state
+        // dispatch): the table's choice made here, so that a lane whose entry lies ahead
+        // in the run order goes on in this trip; a state set to a constant in this run
+        // picks its entry at compile time. Counts: this run's, the jump's taken
+        // correction, the br_table run's and its entry's correction.
+        const DInstr &B = P.code[tgt];
+        const uint32_t ba = B.w1 & 0xFFFFu, nb = B.w1 >> 16;
+        add_cnt(int64_t(r.cnt) + int16_t(last.w2 >> 16) + runs[size_t(brt_thread(tgt))].cnt);
+        int64_t kc = -1;   // the state cell's constant, if this run sets it last
+        for (uint32_t i = nbody; i-- > 0;) {
+          const DInstr &I = P.code[r.pc + i];
+          std::vector<uint32_t> w;
+          written(I, &w);
+          if (std::find(w.begin(), w.end(), ba) == w.end()) continue;
+          if (op_of(I) == OP_CONST32 && (I.w2 & 0xFFFFu) == ba) kc = I.w3;
+          break;
+        }
+        if (kc >= 0) {
+          const uint32_t q = std::min<uint32_t>(uint32_t(kc), nb);
+          const uint32_t t = P.brtab[2 * (B.w3 + q)];
+          e.l("v_mov_b32 %s, 0x%x", VPC, t);
+          add_cnt(int32_t(P.brtab[2 * (B.w3 + q) + 1]));
+          if (!ix.has(t)) out_if("exec");
+          join_batch(t, "exec");
           salu_moved = true;
-        } else if (lop == OP_BR_TABLE) {
-          emit_br_table(e, last);   // Y0 = target, Y1 = correction
+        } else {
+          emit_br_table(e, B);
           e.l("v_mov_b32 %s, %s", VPC, Y0);
           e.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, Y1);
-          add_cnt(r.cnt);
-          br_table_outs(last);
-        } else if (lop == OP_CALL) {
-          std::vector<uint8_t> dead;
-          if (start.count(tgt)) dead = dead_zeros(P, runs[start[tgt]]);
-          emit_call(e, last, e.pc, dead.empty() ? nullptr : &dead);
-          e.l("v_mov_b32 %s, 0x%x", VPC, tgt);
-          add_cnt(r.cnt);
-          if (!in_region(tgt)) out_if("exec");
-        } else if (lop == OP_RET) {
-          // per lane: the call stack past its LDS part and the entry function's return
-          // leave (the C++ step); the others pop their own return record
-          const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
-          e.l("v_cmp_lt_u32_e64 %s, s93, v102", T2);
-          e.leave_if_t2();
-          if (e.ret_pf_done) {
-            e.l("v_mov_b32 %s, v113", Y1);
-          } else {
-            e.l("v_lshl_add_u32 %s, v102, 8, v103", X1);
-            e.l("v_subrev_u32_e32 %s, 0x100, %s", X1, X1);
-            e.l("ds_read_b32 %s, %s", Y1, X1);
-            e.l("s_waitcnt lgkmcnt(0)");
-          }
-          e.l("v_and_b32_e32 %s, 0xfffff, %s", X0, Y1);
-          e.l("v_cmp_eq_u32_e32 vcc, 0xfffff, %s", X0);
-          e.l("s_mov_b64 %s, vcc", T2);
-          e.leave_if_t2();
-          e.l("v_subrev_u32_e32 v102, 1, v102");
-          for (uint32_t q = 0; q < nres; q++)
-            if (a != fb) e.l("v_mov_b32 %s, %s", e.v(fb + q), e.v(a + q));
-          e.l("v_mov_b32 %s, %s", VPC, X0);
-          add_cnt(r.cnt);
-          std::vector<uint32_t> outs = ind_out;
-          const auto it = ret_out.find(func_of(e.pc));
-          if (it != ret_out.end()) outs.insert(outs.end(), it->second.begin(), it->second.end());
-          std::sort(outs.begin(), outs.end());
-          outs.erase(std::unique(outs.begin(), outs.end()), outs.end());
-          for (uint32_t t : outs) {
-            e.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", t, X0);
-            e.l("s_and_b64 s[68:69], vcc, exec");
-            out_if("s[68:69]");
-          }
-        } else {   // falls through into the instruction after the run
-          e.l("v_mov_b32 %s, 0x%x", VPC, fall);
-          add_cnt(r.cnt);
-          if (!in_region(fall)) out_if("exec");
-          join_batch(fall, "exec");
-          salu_moved = true;
+          br_table_outs(B);
         }
-        e.drain();
-      }
-      std::string code = sched_on ? e.o.substr(0, at) + schedule(e.o.substr(at)) : e.o;
-      code += e.stage_end + ":\n";
-      code += "s_mov_b64 exec, s[96:97]\n";
-      if (st == 1 && batch_on && !(smask_on && salu_moved && !is_scan[k])) {   // (moved lanes: the rest of its batch)
-        // Only the tests of runs its lanes can go to: a test on TPC (a run with a stage A)
-        // sees no move, and a run whose exits are known (a jump, a branch, falling through,
-        // a jump onto a br_table's run) moves lanes only onto those pcs.
-        std::vector<uint32_t> succ;
-        bool known = !is_scan[k] && !fwd_ok[k] && pf_from[k] < 0 && pf_to[k] < 0;
-        if (known) {
-          const uint32_t fall = r.pc + r.len;
-          if (lop == OP_JMP) {
-            const int q = brt_on && start.count(last.w3) && runs[start[last.w3]].len == 1 &&
-                                  op_of(P.code[last.w3]) == OP_BR_TABLE
-                              ? int(start[last.w3]) : -1;
-            if (q >= 0) {
-              const DInstr &B = P.code[last.w3];
-              for (uint32_t t = 0; t <= (B.w1 >> 16); t++) succ.push_back(P.brtab[2 * (B.w3 + t)]);
-            } else {
-              succ.push_back(last.w3);
-            }
-          } else if (is_branch_op(lop)) {
-            succ = {fall, last.w3};
-          } else if (!ends_run(lop)) {
-            succ.push_back(fall);
-          } else {
-            known = false;
-          }
+      } else if (lop == OP_JMP) {
+        e.l("v_mov_b32 %s, 0x%x", VPC, tgt);
+        add_cnt(int64_t(r.cnt) + int16_t(last.w2 >> 16));
+        if (!ix.has(tgt)) out_if("exec");
+        join_batch(tgt, "exec");
+        salu_moved = true;
+      } else if (lop == OP_BR_TABLE) {
+        emit_br_table(e, last);   // Y0 = target, Y1 = correction
+        e.l("v_mov_b32 %s, %s", VPC, Y0);
+        e.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, Y1);
+        add_cnt(r.cnt);
+        br_table_outs(last);
+      } else if (lop == OP_CALL) {
+        std::vector<uint8_t> dead;
+        if (ix.has(tgt)) dead = dead_zeros(P, runs[ix.at(tgt)]);
+        emit_call(e, last, e.pc, dead.empty() ? nullptr : &dead);
+        e.l("v_mov_b32 %s, 0x%x", VPC, tgt);
+        add_cnt(r.cnt);
+        if (!ix.has(tgt)) out_if("exec");
+      } else if (lop == OP_RET) {
+        // per lane: the call stack past its LDS part and the entry function's return
+        // leave (the C++ step); the others pop their own return record
+        const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
+        e.l("v_cmp_lt_u32_e64 %s, s93, v102", T2);
+        e.leave_if_t2();
+        if (e.ret_pf_done) {
+          e.l("v_mov_b32 %s, v113", Y1);
+        } else {
+          e.l("v_lshl_add_u32 %s, v102, 8, v103", X1);
+          e.l("v_subrev_u32_e32 %s, 0x100, %s", X1, X1);
+          e.l("ds_read_b32 %s, %s", Y1, X1);
+          e.l("s_waitcnt lgkmcnt(0)");
         }
-        Em rb;
-        for (uint32_t j = k + 1; j <= blast[k]; j++) {
-          if (known && (split[j] || std::find(succ.begin(), succ.end(), runs[j].pc) == succ.end())) continue;
-          b_cmp(rb, j);
+        e.l("v_and_b32_e32 %s, 0xfffff, %s", X0, Y1);
+        e.l("v_cmp_eq_u32_e32 vcc, 0xfffff, %s", X0);
+        e.l("s_mov_b64 %s, vcc", T2);
+        e.leave_if_t2();
+        e.l("v_subrev_u32_e32 v102, 1, v102");
+        for (uint32_t q = 0; q < nres; q++)
+          if (a != fb) e.l("v_mov_b32 %s, %s", e.v(fb + q), e.v(a + q));
+        e.l("v_mov_b32 %s, %s", VPC, X0);
+        add_cnt(r.cnt);
+        std::vector<uint32_t> outs = tp.ind_out;
+        const auto it = tp.ret_out.find(ix.func_of(e.pc));
+        if (it != tp.ret_out.end()) outs.insert(outs.end(), it->second.begin(), it->second.end());
+        std::sort(outs.begin(), outs.end());
+        outs.erase(std::unique(outs.begin(), outs.end()), outs.end());
+        for (uint32_t t : outs) {
+          e.l("v_cmp_eq_u32_e32 vcc, 0x%x, %s", t, X0);
+          e.l("s_and_b64 s[68:69], vcc, exec");
+          out_if("s[68:69]");
         }
-        code += rb.o;
+      } else {   // falls through into the instruction after the run
+        e.l("v_mov_b32 %s, 0x%x", VPC, fall);
+        add_cnt(r.cnt);
+        if (!ix.has(fall)) out_if("exec");
+        join_batch(fall, "exec");
+        salu_moved = true;
       }
-      // the test's branch: past the stage inline (a stage short enough for the branch's
-      // reach, 2^15 dwords: <= 2,048 lines of at most 12 bytes), else to it out of line
-      const std::string mark = "@@" + L + "@@\n", ret = std::string(stage_name[st]) + "r" + std::to_string(k);
-      const size_t at_m = h.o.find(mark);
-      if (at_m == std::string::npos) return "";
-      if (inline_on && std::count(code.begin(), code.end(), '\n') <= 2048) {
-        const std::string al = ".p2align 2\n";   // (in the chain: no alignment)
-        if (code.compare(0, al.size(), al) == 0) code.erase(0, al.size());
-        h.o.replace(at_m, mark.size(), "s_cbranch_scc0 " + ret + "\n" + code);
-        oob += e.tail;
-        continue;
-      }
-      h.o.replace(at_m, mark.size(), "s_cbranch_scc1 " + L + "\n");
-      code += "s_branch " + ret + "\n";
-      code += e.tail;
-      (st ? oob : ooa) += code;
+      e.drain();
     }
+    std::string code = kn.jit_sched ? e.o.substr(0, at) + schedule(e.o.substr(at), kn) : e.o;
+    code += e.stage_end + ":\n";
+    code += "s_mov_b64 exec, s[96:97]\n";
+    if (st == 1 && kn.trip_batch && !(kn.trip_smask && salu_moved && !tp.is_scan[k])) {   // (moved lanes: the rest of its batch)
+      // Only the tests of runs its lanes can go to: a test on TPC (a run with a stage A)
+      // sees no move, and a run whose exits are known (a jump, a branch, falling through,
+      // a jump onto a br_table's run) moves lanes only onto those pcs.
+      std::vector<uint32_t> succ;
+      bool known = !tp.is_scan[k] && !tp.fwd_ok[k] && tp.pf_from[k] < 0 && tp.pf_to[k] < 0;
+      if (known) {
+        const uint32_t fall = r.pc + r.len;
+        if (lop == OP_JMP) {
+          const int q = kn.brt_thread && ix.has(last.w3) && runs[ix.at(last.w3)].len == 1 &&
+                                op_of(P.code[last.w3]) == OP_BR_TABLE
+                            ? int(ix.at(last.w3)) : -1;
+          if (q >= 0) {
+            const DInstr &B = P.code[last.w3];
+            for (uint32_t t = 0; t <= (B.w1 >> 16); t++) succ.push_back(P.brtab[2 * (B.w3 + t)]);
+          } else {
+            succ.push_back(last.w3);
+          }
+        } else if (is_branch_op(lop)) {
+          succ = {fall, last.w3};
+        } else if (!ends_run(lop)) {
+          succ.push_back(fall);
+        } else {
+          known = false;
+        }
+      }
+      Em rb(t);
+      for (uint32_t j = k + 1; j <= tp.blast[k]; j++) {
+        if (known && (tp.split[j] || std::find(succ.begin(), succ.end(), runs[j].pc) == succ.end())) continue;
+        b_cmp(rb, j);
+      }
+      code += rb.o;
+    }
+// Inline stages (WB_TRIP_INLINE=0 turns it off): a run's stage code sits in the test
+// chain right after its test, which branches past it when no lane is there -- a stage
+// that takes lanes costs no taken branch (out of line it costs two: there and back), one
+// that takes none costs one. Taken branches are what the trips' scalar stream waits on (a
+// taken branch refetches: ~20 cycles, tools/ubench/lat.hip); C3 1 MiB +6% with stage B
+// inline (profiles/r06zb_bench_c3_*).
+    // the test's branch: past the stage inline (a stage short enough for the branch's
+    // reach, 2^15 dwords: <= 2,048 lines of at most 12 bytes), else to it out of line
+    const std::string mark = "@@" + L + "@@\n", ret = std::string(stage_name[st]) + "r" + std::to_string(k);
+    const size_t at_m = h.o.find(mark);
+    if (at_m == std::string::npos) return false;
+    if (kn.trip_inline && std::count(code.begin(), code.end(), '\n') <= 2048) {
+      const std::string al = ".p2align 2\n";   // (in the chain: no alignment)
+      if (code.compare(0, al.size(), al) == 0) code.erase(0, al.size());
+      h.o.replace(at_m, mark.size(), "s_cbranch_scc0 " + ret + "\n" + code);
+      oob += e.tail;
+      continue;
+    }
+    h.o.replace(at_m, mark.size(), "s_cbranch_scc1 " + L + "\n");
+    code += "s_branch " + ret + "\n";
+    code += e.tail;
+    (st ? oob : ooa) += code;
   }
-  body += h.o + ooa + oob;
+  return true;
+}
+
+}  // namespace
+
+// hybrid: only the trips' code (Ltin, the trip loop, the runs' stages, the exits), for
+// jit_source's SIMT code object, whose Lsched sends diverged waves to Ltin; a trip after
+// which every lane is at one pc goes back to Lsched (SIMT scheduling, direct run-to-run
+// jumps) -- converged phases (C3's fill and checksum loops; modules like mt19937 whose
+// addresses merely look divergent to the static analysis) run without trips.
+std::string trip_source(const JitTarget &t, const JitKnobs &kn, const RunIndex &ix,
+                        const std::vector<JitRun> &runs, bool hybrid) {
+  // NaN fixes only where the payload can be observed (WB_NANOBS=0: everywhere)
+  const std::vector<uint8_t> nob = kn.nanobs ? nan_observable(t.P, kn) : std::vector<uint8_t>();
+  const TripPlan tp = plan_trips(t, kn, ix, runs);
+  TripEmit te(t, kn, ix, runs, nob, hybrid, tp);
+  std::string body;
+  if (!hybrid)
+  if (!hybrid)
+    body += "s_getpc_b64 s[6:7]\nLpt:\ns_add_u32 s6, s6, Ltab - Lpt\ns_addc_u32 s7, s7, 0\n"
+            "s_mov_b32 %0, s6\ns_mov_b32 %1, s7\n"
+            "s_getpc_b64 s[8:9]\nLpe:\ns_add_u32 s8, s8, Lend - Lpe\ns_addc_u32 s9, s9, 0\n"
+            "s_setpc_b64 s[8:9]\n";
+  te.entry_stubs();
+  te.trip_entry();
+  te.tests_a();
+  te.tests_b();
+  te.after_trip();
+  for (uint32_t k = 0; k < te.nr; k++)
+    if (!te.run_stages(k)) return "";
+  body += te.h.o + te.ooa + te.oob;
   if (hybrid) return body;
   body = resolve_jumps(body);
   body += ".p2align 3\nLtab:\n";
@@ -3799,6 +3632,7 @@ std::string trip_source(const Program &P, const std::vector<JitRun> &runs, uint3
          "}\n";
   return src;
 }
+
 
 // ---------------------------------------------------------------- constant folding
 // Cells read and written by the instructions the planner below lets stand between a fold
@@ -3939,14 +3773,9 @@ FoldPlan plan_folds(const Program &P, const JitRun &r, uint32_t nbody,
 
 // Whether a function can reach itself through calls: a cycle among direct calls (CALL,
 // TAIL_CALL), or any indirect call (its targets are not known here)
-bool recursive(const Program &P) {
-  std::map<uint32_t, uint32_t> fentry;   // entry pc -> function
-  for (uint32_t f = 0; f < P.funcs.size(); f++)
-    if (!P.funcs[f].imported) fentry[P.funcs[f].entry_pc] = f;
-  auto func_of = [&](uint32_t pc) -> int64_t {
-    auto it = fentry.upper_bound(pc);
-    return it == fentry.begin() ? -1 : int64_t(std::prev(it)->second);
-  };
+bool jit::recursive(const Program &P) {
+  const RunIndex ix(P, {});
+  auto func_of = [&](uint32_t pc) { return ix.func_of(pc); };
   const size_t nf = P.funcs.size();
   std::vector<std::vector<uint32_t>> g(nf);
   for (uint32_t pc = 0; pc < P.code.size(); pc++) {
@@ -3973,164 +3802,215 @@ bool recursive(const Program &P) {
   return false;
 }
 
-std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32_t glog,
-                       const JitCost *cost, bool simt, bool trip, const std::vector<uint32_t> *xinfo,
-                       uint32_t xlog, uint32_t mem_pages) {
-  if (cost) simt = false;
-  // (extra memories: their accesses compile only against the context's word offsets)
-  if (!P.xmems.empty() && (!xinfo || xinfo->size() < 2 * P.xmems.size())) return "";
-  struct XinfoScope {
-    XinfoScope(const std::vector<uint32_t> *x, uint32_t lg, uint32_t mp) { g_xinfo = x; g_xlog = lg; g_mem_pages = mp; }
-    ~XinfoScope() { g_xinfo = nullptr; g_xlog = 0; g_mem_pages = 65536; }
-  } xscope(xinfo, xlog, mem_pages);
-  // trip mode beside SIMT scheduling (hybrid, the default) or alone (WB_HYBRID=0)
-  const bool trips = trip && simt && runs.size() <= kTripMaxRuns;
-  const bool hybrid = trips && !(getenv("WB_HYBRID") && getenv("WB_HYBRID")[0] == '0');
-  if (trips && !hybrid) return trip_source(P, runs, glog, false);
-  // NaN fixes only where the payload can be observed (WB_NANOBS=0: everywhere)
-  const bool nob_on = !(getenv("WB_NANOBS") && getenv("WB_NANOBS")[0] == '0');
-  const std::vector<uint8_t> nob = nob_on ? nan_observable(P) : std::vector<uint8_t>();
-  // plain cell liveness (constant folds, fused any_true); WB_FOLD=0 turns both off
-  std::vector<std::vector<uint64_t>> live;
-  if (!(getenv("WB_FOLD") && getenv("WB_FOLD")[0] == '0')) nan_observable(P, &live);
-  // an f64x2 compare feeding a fused any_true hands its lane masks to the branch (C5
-  // 1.435e13 -> 1.475e13, profiles/r03ab_bench.json; WB_CMPANY=0 turns it off)
-  const bool cmp_any_on = !(getenv("WB_CMPANY") && getenv("WB_CMPANY")[0] == '0');
-  // which divergence events stay in the core (debug aid): 1 split branches, 2 split
-  // returns, 4 reaching a waiting lane / the count limit (else the core leaves as without
-  // SIMT)
+// The one place the code generator reads its environment (JitKnobs: one line per knob)
+JitKnobs jit::read_knobs() {
+  auto on = [](const char *name) {
+    const char *v = getenv(name);
+    return !(v && v[0] == '0');
+  };
+  JitKnobs k;
+  k.hybrid = on("WB_HYBRID");
+  k.nanobs = on("WB_NANOBS");
+  k.fold = on("WB_FOLD");
+  k.cmpany = on("WB_CMPANY");
+  k.jit_sched = on("WB_JIT_SCHED");
+  k.sched_stores = on("WB_SCHED_STORES");
+  k.load_batch = on("WB_LOAD_BATCH");
+  k.depth = on("WB_DEPTH");
+  k.inline_calls = on("WB_INLINE");
+  k.fwd = on("WB_FWD");
+  k.fwd_store = on("WB_FWD_STORE");
+  k.fwd_alias = on("WB_FWD_ALIAS");
+  k.ret_pf = on("WB_RET_PF");
+  k.brt_thread = on("WB_BRT_THREAD");
+  k.trip_fwd = on("WB_TRIP_FWD");
+  k.trip_fwdchk = on("WB_TRIP_FWDCHK");
+  k.trip_mad = on("WB_TRIP_MAD");
+  k.trip_split = on("WB_TRIP_SPLIT");
+  k.trip_pf = on("WB_TRIP_PF");
+  k.trip_x4 = on("WB_TRIP_X4");
+  k.trip_scanbf = on("WB_TRIP_SCANBF");
+  k.trip_batch = on("WB_TRIP_BATCH");
+  k.trip_inline = on("WB_TRIP_INLINE");
+  k.trip_smask = on("WB_TRIP_SMASK");
+  k.trip_cmpbr = on("WB_TRIP_CMPBR");
+  k.trip_chain = on("WB_TRIP_CHAIN");
+  k.trip_guard = on("WB_TRIP_GUARD");
+  const char *c1 = getenv("WB_TRIP_CONV1");
+  k.trip_conv1 = c1 && c1[0] == '1';
   const char *sxe = getenv("WB_SIMT_X");
-  const unsigned sx = simt ? (sxe ? unsigned(atoi(sxe)) : 7u) : 0u;
-  const char *se = getenv("WB_JIT_SCHED");   // 0: keep program order (A/B measurement aid)
-  const bool sched = !(se && se[0] == '0');
-  const char *lbe = getenv("WB_LOAD_BATCH");   // 0: loads in program order (A/B aid)
-  const bool batching = !(lbe && lbe[0] == '0');
-  // One asm statement holds every run (behind a jump) and a table of their offsets from
-  // the table itself; the kernel reads the table and writes the absolute addresses.
-  std::string body;
-  body += "s_getpc_b64 s[6:7]\nLpt:\ns_add_u32 s6, s6, Ltab - Lpt\ns_addc_u32 s7, s7, 0\n"
-          "s_mov_b32 %0, s6\ns_mov_b32 %1, s7\n"
-          "s_getpc_b64 s[8:9]\nLpe:\ns_add_u32 s8, s8, Lend - Lpe\ns_addc_u32 s9, s9, 0\n"
-          "s_setpc_b64 s[8:9]\n";
-  // Recursive modules pick groups by call-stack height first (sched_block); their split
-  // branches go through that pick too (the pc-only shortcut, Lbf, would undo it).
-  // WB_DEPTH=0: pc-only picks everywhere (A/B aid)
-  const bool depth_pick = simt && !(getenv("WB_DEPTH") && getenv("WB_DEPTH")[0] == '0') &&
-                          recursive(P);
-  if (simt) body += simt_sched(hybrid, depth_pick);
-  // run index by start pc: a transfer to one jumps straight to its code
-  std::map<uint32_t, size_t> start;
-  for (size_t k = 0; k < runs.size(); k++) start[runs[k].pc] = k;
+  k.simt_x = sxe ? unsigned(atoi(sxe)) : 7u;
+  const char *tse = getenv("WB_TRIP_SCAN");
+  k.trip_scan = tse ? std::min<uint32_t>(uint32_t(atoi(tse)), kTripScan) : kTripScan;
+  const char *cpe = getenv("WB_TRIP_CONVP");
+  k.trip_convp = cpe ? std::min(8u, std::max(1u, uint32_t(atoi(cpe)))) : 4u;
+  const char *ose = getenv("WB_TRIP_OUTSH");
+  k.trip_outsh = ose ? std::max(0, std::min(6, atoi(ose))) : 6;
+  k.nanobs_list = getenv("WB_NANOBS_LIST");
+  return k;
+}
+
+namespace {
+
+// What jit_source decides about the module's runs before it writes any of them
+struct SimtPlan {
+  std::vector<std::vector<uint64_t>> live;   // plain cell liveness (constant folds, fused any_true)
   // a return's likely targets: the instruction after each direct call of its function
-  // (functions are laid out in order of entry pc)
-  std::map<uint32_t, uint32_t> fentry;   // entry pc -> function index
-  for (uint32_t f = 0; f < P.funcs.size(); f++)
-    if (!P.funcs[f].imported) fentry[P.funcs[f].entry_pc] = f;
-  auto func_of = [&](uint32_t pc) -> int64_t {
-    auto it = fentry.upper_bound(pc);
-    return it == fentry.begin() ? -1 : int64_t(std::prev(it)->second);
-  };
   std::map<uint32_t, std::vector<uint32_t>> ret_sites;   // function -> return pcs
-  for (uint32_t pc = 0; pc < P.code.size(); pc++)
-    if (op_of(P.code[pc]) == OP_CALL) {
-      const int64_t f = func_of(P.code[pc].w3);
-      if (f >= 0) ret_sites[uint32_t(f)].push_back(pc + 1);
-    }
-  // Inlined call: a leaf callee that is one compiled run ending in its return runs in
-  // the calling run's code, its cells `off` = L - fb higher (above the caller's live
-  // cells, which therefore need no spill), its arguments already in place at L.., its
-  // result moved to L.., and the caller goes on after its POST_CALL (no call-stack
-  // traffic, no return-record check). A leave inside the callee first makes the call real
-  // (spill, return record, callee cells down to fb) so the C++ step meets the reference
-  // layout. inline_of: the callee's run and the post-call run, or -1.
-  const bool inl_env = !(getenv("WB_INLINE") && getenv("WB_INLINE")[0] == '0');
-  auto inline_of = [&](size_t k, int64_t *inl_f, int64_t *inl_post) {
-    *inl_f = *inl_post = -1;
-    const JitRun &r = runs[k];
-    const DInstr &last = P.code[r.pc + r.len - 1];
-    const uint32_t tgt = last.w3, cpc = r.pc + r.len - 1;
-    if (op_of(last) != OP_CALL || cost || !inl_env || !start.count(tgt)) return;
-    const JitRun &rf = runs[start[tgt]];
-    const uint32_t L = last.w1 & 0xFFFFu, fb = P.global_cells;
-    const uint32_t off = L - fb;
-    auto nx = fentry.upper_bound(tgt);
-    const uint32_t fend = nx == fentry.end() ? uint32_t(P.code.size()) : nx->first;
-    // (a call enters past its callee's ZERO_LOCALS: the call zeroes the locals itself)
-    bool ok = op_of(P.code[rf.pc + rf.len - 1]) == OP_RET && rf.pc + rf.len == fend &&
-              func_of(tgt) >= 0 && L >= fb && off % 2 == 0 && off < 255 &&
-              uint64_t(P.total_cells()) + off <= TC_VF_CELLS;
-    for (uint32_t i = 0; ok && i + 1 < rf.len; i++) {
-      const uint16_t o = op_of(P.code[rf.pc + i]);
-      ok = !ends_run(o) && o != OP_POST_CALL;
-    }
-    auto pm = start.find(cpc + 1);
-    ok = ok && pm != start.end() && op_of(P.code[cpc + 1]) == OP_POST_CALL &&
-         (P.code[cpc + 1].w1 & 0xFFFFu) == L;
-    if (ok) { *inl_f = int64_t(start[tgt]); *inl_post = int64_t(pm->second); }
-  };
-  // runs compiled twice more for loop-carried forwarding (FwdPlan): (k, 0) every run,
-  // (R, 1) the copy entered with F valid, (Pp, 2) the post-call copy that enters it
-  const char *fwe = getenv("WB_FWD");   // 0: no forwarding copies (A/B aid)
-  const bool fwd_store = !(getenv("WB_FWD_STORE") && getenv("WB_FWD_STORE")[0] == '0');
-  const bool fwd_alias = !(getenv("WB_FWD_ALIAS") && getenv("WB_FWD_ALIAS")[0] == '0');
-  std::map<size_t, FwdPlan> plans;      // R -> plan
-  std::map<size_t, size_t> loop_of;     // Pp -> R
+  std::vector<int64_t> inl_f, inl_post;   // per run: the inlined callee's run and the post-call run, or -1
+  std::map<size_t, FwdPlan> plans;        // R -> plan
+  std::map<size_t, size_t> loop_of;       // Pp -> R
   std::vector<std::pair<size_t, int>> jobs;
-  for (size_t k = 0; k < runs.size(); k++) jobs.push_back({k, 0});
-  for (size_t k = 0; k < runs.size() && !(fwe && fwe[0] == '0'); k++) {
-    int64_t f, post;
-    inline_of(k, &f, &post);
-    FwdPlan pl;
-    if (f < 0 || loop_of.count(size_t(post)) || size_t(post) == k ||
-        !fwd_plan(P, runs, k, size_t(f), size_t(post), &pl))
-      continue;
-    plans[k] = pl;
-    loop_of[size_t(post)] = k;
-    jobs.push_back({k, 1});
-    jobs.push_back({size_t(post), 2});
-  }
   // runs an inlined call returns into (past their POST_CALL: Lpa) never read their RET
   // record along with the POST_CALL (Em::ret_pf), which that path skips
-  std::vector<uint8_t> inl_target(runs.size(), 0);
-  for (size_t k = 0; k < runs.size(); k++) {
-    int64_t f, post;
-    inline_of(k, &f, &post);
-    if (post >= 0) inl_target[size_t(post)] = 1;
+  std::vector<uint8_t> inl_target;
+};
+
+// Inlined call: a leaf callee that is one compiled run ending in its return runs in
+// the calling run's code, its cells `off` = L - fb higher (above the caller's live
+// cells, which therefore need no spill), its arguments already in place at L.., its
+// result moved to L.., and the caller goes on after its POST_CALL (no call-stack
+// traffic, no return-record check). A leave inside the callee first makes the call real
+// (spill, return record, callee cells down to fb) so the C++ step meets the reference
+// layout. inline_of: the callee's run and the post-call run, or -1.
+static void inline_of(const JitTarget &t, const JitKnobs &kn, const RunIndex &ix,
+                      const std::vector<JitRun> &runs, size_t k, int64_t *inl_f, int64_t *inl_post) {
+  const Program &P = t.P;
+  *inl_f = *inl_post = -1;
+  const JitRun &r = runs[k];
+  const DInstr &last = P.code[r.pc + r.len - 1];
+  const uint32_t tgt = last.w3, cpc = r.pc + r.len - 1;
+  if (op_of(last) != OP_CALL || t.cost || !kn.inline_calls || !ix.has(tgt)) return;
+  const JitRun &rf = runs[ix.at(tgt)];
+  const uint32_t L = last.w1 & 0xFFFFu, fb = P.global_cells;
+  const uint32_t off = L - fb;
+  const uint32_t fend = ix.func_end(tgt);
+  // (a call enters past its callee's ZERO_LOCALS: the call zeroes the locals itself)
+  bool ok = op_of(P.code[rf.pc + rf.len - 1]) == OP_RET && rf.pc + rf.len == fend &&
+            ix.func_of(tgt) >= 0 && L >= fb && off % 2 == 0 && off < 255 &&
+            uint64_t(P.total_cells()) + off <= TC_VF_CELLS;
+  for (uint32_t i = 0; ok && i + 1 < rf.len; i++) {
+    const uint16_t o = op_of(P.code[rf.pc + i]);
+    ok = !ends_run(o) && o != OP_POST_CALL;
   }
-  const bool ret_pf_on = !(getenv("WB_RET_PF") && getenv("WB_RET_PF")[0] == '0');
-  for (size_t jb = 0; jb < jobs.size(); jb++) {
-    const size_t k = jobs[jb].first;
-    const int var = jobs[jb].second;
-    const JitRun &r = runs[k];
-    Em e;
-    e.ret_pf = ret_pf_on && !cost && !inl_target[k] && ret_prefetch_run(P, r);
-    e.g = glog;
-    e.run = uint32_t(k + size_t(var) * 2 * runs.size());   // (stub labels apart)
-    const std::string K = std::to_string(k) + (var == 1 ? "c" : var == 2 ? "p" : "");
-    if (!nob.empty()) e.nanobs = &nob;
+  auto pm = ix.start.find(cpc + 1);
+  ok = ok && pm != ix.start.end() && op_of(P.code[cpc + 1]) == OP_POST_CALL &&
+       (P.code[cpc + 1].w1 & 0xFFFFu) == L;
+  if (ok) { *inl_f = int64_t(ix.at(tgt)); *inl_post = int64_t(pm->second); }
+}
+
+SimtPlan plan_simt(const JitTarget &t, const JitKnobs &kn, const RunIndex &ix, const std::vector<JitRun> &runs) {
+  const Program &P = t.P;
+  SimtPlan pl;
+  // (WB_FOLD=0 turns the folds and the fused any_true off)
+  if (kn.fold) nan_observable(P, kn, &pl.live);
+  for (uint32_t pc = 0; pc < P.code.size(); pc++)
+    if (op_of(P.code[pc]) == OP_CALL) {
+      const int64_t f = ix.func_of(P.code[pc].w3);
+      if (f >= 0) pl.ret_sites[uint32_t(f)].push_back(pc + 1);
+    }
+  pl.inl_f.assign(runs.size(), -1);
+  pl.inl_post.assign(runs.size(), -1);
+  pl.inl_target.assign(runs.size(), 0);
+  for (size_t k = 0; k < runs.size(); k++) {
+    inline_of(t, kn, ix, runs, k, &pl.inl_f[k], &pl.inl_post[k]);
+    if (pl.inl_post[k] >= 0) pl.inl_target[size_t(pl.inl_post[k])] = 1;
+  }
+  // runs compiled twice more for loop-carried forwarding (FwdPlan): (k, 0) every run,
+  // (R, 1) the copy entered with F valid, (Pp, 2) the post-call copy that enters it
+  for (size_t k = 0; k < runs.size(); k++) pl.jobs.push_back({k, 0});
+  for (size_t k = 0; k < runs.size() && kn.fwd; k++) {
+    const int64_t f = pl.inl_f[k], post = pl.inl_post[k];
+    FwdPlan fp;
+    if (f < 0 || pl.loop_of.count(size_t(post)) || size_t(post) == k ||
+        !fwd_plan(P, runs, k, size_t(f), size_t(post), &fp))
+      continue;
+    pl.plans[k] = fp;
+    pl.loop_of[size_t(post)] = k;
+    pl.jobs.push_back({k, 1});
+    pl.jobs.push_back({size_t(post), 2});
+  }
+  return pl;
+}
+
+// what every run of one jit_source call is compiled against
+struct SimtCtx {
+  const JitTarget &t;
+  const JitKnobs &kn;
+  const RunIndex &ix;
+  const std::vector<JitRun> &runs;
+  const SimtPlan &pl;
+  const std::vector<uint8_t> &nob;   // nan_observable (empty: a fix for every NaN)
+  unsigned sx;                       // the divergence events kept in the core (JitKnobs::simt_x; 0 without SIMT)
+  bool hybrid, depth_pick;
+};
+
+// One job: run k's code, or one of its forwarding copies (var 1: the copy entered with F
+// valid, 2: the post-call copy that enters it)
+struct RunCompile {
+  const JitTarget &t;
+  const JitKnobs &kn;
+  const RunIndex &ix;
+  const std::vector<JitRun> &runs;
+  const SimtPlan &pl;
+  const Program &P;
+  const JitCost *const cost;
+  const std::vector<uint8_t> &nob;
+  const std::vector<std::vector<uint64_t>> &live;
+  const unsigned sx;
+  const bool hybrid, depth_pick;
+  const size_t k;
+  const int var;
+  const JitRun &r;
+  const std::string K, xs;
+  const DInstr &last;
+  const uint16_t lop;
+  // Where the run goes on: the instruction after it (fall-through, untaken branch), a
+  // call's or branch's target, or (return) the popped return pc.
+  const uint32_t fall, tgt;
+  bool preload = false;
+  Em e;
+  // metered: the price of each way out
+  uint64_t c_fall = 0;
+  int64_t c_adj = 0;
+  std::string extra;   // SIMT split code, placed after the run
+  uint32_t fuse_cell = ~0u;
+  bool cmp_any = false;
+  int lab = 0, nfast = 0;
+
+  RunCompile(const SimtCtx &c, size_t k_, int var_)
+      : t(c.t), kn(c.kn), ix(c.ix), runs(c.runs), pl(c.pl), P(c.t.P), cost(c.t.cost), nob(c.nob),
+        live(c.pl.live), sx(c.sx), hybrid(c.hybrid), depth_pick(c.depth_pick), k(k_), var(var_),
+        r(c.runs[k_]), K(std::to_string(k_) + (var_ == 1 ? "c" : var_ == 2 ? "p" : "")), xs("Lxs" + K),
+        last(P.code[r.pc + r.len - 1]), lop(op_of(last)), fall(r.pc + r.len),
+        tgt((lop == OP_CALL || lop == OP_TAIL_CALL || is_branch_op(lop)) ? last.w3 : 0),
+        // (stub labels apart)
+        e(c.t, uint32_t(k_ + size_t(var_) * 2 * c.runs.size()), c.nob.empty() ? nullptr : &c.nob) {}
+
+  // a forwarding loop's post-call copy enters its run's forwarding copy
+  const char *copy_sfx(size_t q) const {
+    auto it = pl.loop_of.find(k);
+    return var == 2 && it != pl.loop_of.end() && it->second == q ? "c" : "";
+  }
+
+  // the run's label, the prefetch of where it goes on, the entry checks
+  void entry() {
+    e.ret_pf = kn.ret_pf && !cost && !pl.inl_target[k] && ret_prefetch_run(P, r);
     e.l(".p2align 6");
     e.l("Lb%s:", K.c_str());
-    const DInstr &last = P.code[r.pc + r.len - 1];
-    const uint16_t lop = op_of(last);
     // Where the run goes on: the instruction after it (fall-through, untaken branch), a
     // call's or branch's target, or (return) the popped return pc. The instruction after
     // the run is prefetched into both banks while the run works, unless it starts a
     // compiled run itself (then the code jumps there) or the run calls.
-    const uint32_t fall = r.pc + r.len;
-    const uint32_t tgt = (lop == OP_CALL || lop == OP_TAIL_CALL || is_branch_op(lop)) ? last.w3 : 0;
     const uint32_t pre = lop == OP_CALL || lop == OP_TAIL_CALL ? tgt : fall;
-    const bool preload = lop != OP_RET && lop != OP_JMP && lop != OP_BR_TABLE && !start.count(pre);
-    e.fb = P.global_cells;
-    e.prog = &P;
+    preload = lop != OP_RET && lop != OP_JMP && lop != OP_BR_TABLE && !ix.has(pre);
     if (preload) {
       e.l("s_waitcnt lgkmcnt(0)");
       e.l("s_mov_b32 s68, 0x%x", pre * 32u);
       e.l("s_load_dwordx8 s[76:83], s[60:61], s68");
       e.l("s_load_dwordx8 s[84:91], s[60:61], s68 offset:0x20");
     }
-    // metered: the price of each way out, and the entry check against the dearest
-    uint64_t c_fall = 0;
-    int64_t c_adj = 0;
+    // metered: the entry check against the dearest way out
     if (cost) {
       e.metered = true;
       for (uint32_t i = 0; i < r.len; i++) c_fall += cost->full(P, r.pc + i);
@@ -4148,40 +4028,37 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
     // POST_CALL ... CALL: one call-stack check at the start for both (the POST_CALL pops
     // `pop` slots, the CALL pushes n + 1), leaving before the run when either would.
     // Not where an inlined call enters past the POST_CALL (Lpa), nor for an inlined CALL.
-    {
-      int64_t f0 = -1, p0 = -1;
-      inline_of(k, &f0, &p0);
-      const DInstr &first = P.code[r.pc];
-      const uint32_t fbc = P.global_cells;
-      if (!inl_target[k] && f0 < 0 && lop == OP_CALL && r.len >= 2 &&
-          op_of(first) == OP_POST_CALL && (first.w1 & 0xFFFFu) >= fbc &&
-          (last.w1 & 0xFFFFu) >= fbc) {
-        const uint32_t pop = (first.w1 & 0xFFFFu) - fbc, push = (last.w1 & 0xFFFFu) - fbc + 1;
-        e.pc = r.pc;
-        if (push > pop) {
-          e.l("v_add_u32_e32 %s, %u, v102", X0, push - pop);
-          e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
-        } else {
-          e.l("v_cmp_lt_u32_e64 %s, s93, v102", T2);
-        }
-        e.leave_if_t2();
-        e.call_checked = true;
+    const DInstr &first = P.code[r.pc];
+    const uint32_t fbc = P.global_cells;
+    if (!pl.inl_target[k] && pl.inl_f[k] < 0 && lop == OP_CALL && r.len >= 2 &&
+        op_of(first) == OP_POST_CALL && (first.w1 & 0xFFFFu) >= fbc &&
+        (last.w1 & 0xFFFFu) >= fbc) {
+      const uint32_t pop = (first.w1 & 0xFFFFu) - fbc, push = (last.w1 & 0xFFFFu) - fbc + 1;
+      e.pc = r.pc;
+      if (push > pop) {
+        e.l("v_add_u32_e32 %s, %u, v102", X0, push - pop);
+        e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
+      } else {
+        e.l("v_cmp_lt_u32_e64 %s, s93, v102", T2);
       }
+      e.leave_if_t2();
+      e.call_checked = true;
     }
-    std::string extra;   // SIMT split code, placed after the run
+  }
+
+  // the run's instructions but the transfer, scheduled
+  bool body() {
     std::vector<int> lead;
     const std::vector<MemGroup> groups = jit_groups(P, r, &lead);
     const size_t body_at = e.o.size();
-    const std::string xs = "Lxs" + K;
     const uint32_t nbody = ends_run(lop) ? r.len - 1 : r.len;
-    const std::vector<LoadBatch> batches = batching ? load_batches(P, r, nbody, lead)
+    const std::vector<LoadBatch> batches = kn.load_batch ? load_batches(P, r, nbody, lead)
                                                     : std::vector<LoadBatch>();
     size_t nb = 0;
     const FoldPlan fp = plan_folds(P, r, nbody, live, nob, batches);
     // an any_true that only feeds the run's br_if / br_unless (its cell dead where the run
     // goes on): the branch tests the OR of the vector's words itself (SIMT: a split stays in
     // the compiled code, so nothing outside reads the cell)
-    uint32_t fuse_cell = ~0u;
     if ((sx & 1) && !cost && nbody >= 1 && nbody < r.len && !live.empty() &&
         (lop == OP_BR_IF || lop == OP_BR_UNLESS) && !fp.skip[nbody - 1]) {
       const DInstr &A = P.code[r.pc + nbody - 1];
@@ -4195,8 +4072,7 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
     }
     // ... and the f64x2 compare right before it whose mask it reads: the branch takes the
     // compare's lane masks (WB_FOLD=0 turns this off with the rest)
-    bool cmp_any = false;
-    if (fuse_cell != ~0u && nbody >= 2 && !fp.skip[nbody - 2] && cmp_any_on) {
+    if (fuse_cell != ~0u && nbody >= 2 && !fp.skip[nbody - 2] && kn.cmpany) {
       const DInstr &Cm = P.code[r.pc + nbody - 2], &A = P.code[r.pc + nbody - 1];
       const uint16_t co = op_of(Cm);
       bool inb = false;
@@ -4231,553 +4107,558 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
       e.kfold.clear();
       e.fuse_any = false;
       e.cmp_any = false;
-      if (!ok_emit) return "";   // jit_runs only picks compilable instructions
+      if (!ok_emit) return false;   // jit_runs only picks compilable instructions
       e.done += (I.w0 >> 16) & 0xFFu;
       if (cost) e.cdone += cost->full(P, r.pc + i);
       // an inlined call goes on here, after the POST_CALL it makes unnecessary
       if (i == 0 && op_of(I) == OP_POST_CALL) e.l("Lpa%s:", K.c_str());
     }
     e.drain();
-    if (sched) e.o = e.o.substr(0, body_at) + schedule(e.o.substr(body_at));
+    if (kn.jit_sched) e.o = e.o.substr(0, body_at) + schedule(e.o.substr(body_at), kn);
     e.pc = r.pc + r.len - 1;
     e.group = nullptr;
-    // go to pc `to` (PCOFF and CNT set): straight into its compiled run when it has one
-    // (in diverged mode only if that run stops short of the lowest waiting pc, as the
-    // JIT slot would check), else through its TInstr (banks: already loaded for it)
-    int lab = 0;
-    auto go = [&](uint32_t to, bool banks) {
-      auto it = start.find(to);
-      const std::string disp = "Ld" + K + "_" + std::to_string(lab++);
-      if (it != start.end()) {
-        e.l("s_add_u32 s68, s62, 0x%x", (runs[it->second].len - 1) * 32u);
-        e.l("s_cmp_ge_u32 s68, s63");
-        e.l("s_cbranch_scc1 %s", disp.c_str());
-        // (a long jump: the code object can outgrow s_branch's +-128 KiB); a forwarding
-        // loop's post-call copy enters its run's forwarding copy
-        const std::string q = "Lq" + K + "_" + std::to_string(lab);
-        const std::string tl = "Lb" + std::to_string(it->second) +
-                               (var == 2 && loop_of.count(k) && loop_of[k] == it->second ? "c" : "");
-        long_jump(e, tl, q);
-        e.l("%s:", disp.c_str());
-        banks = false;
-      }
+    return true;
+  }
+
+  // go to pc `to` (PCOFF and CNT set): straight into its compiled run when it has one
+  // (in diverged mode only if that run stops short of the lowest waiting pc, as the
+  // JIT slot would check), else through its TInstr (banks: already loaded for it)
+  void go(uint32_t to, bool banks) {
+    auto it = ix.start.find(to);
+    const std::string disp = "Ld" + K + "_" + std::to_string(lab++);
+    if (it != ix.start.end()) {
+      e.l("s_add_u32 s68, s62, 0x%x", (runs[it->second].len - 1) * 32u);
+      e.l("s_cmp_ge_u32 s68, s63");
+      e.l("s_cbranch_scc1 %s", disp.c_str());
+      // (a long jump: the code object can outgrow s_branch's +-128 KiB); a forwarding
+      // loop's post-call copy enters its run's forwarding copy
+      const std::string q = "Lq" + K + "_" + std::to_string(lab);
+      const std::string tl = "Lb" + std::to_string(it->second) +
+                             copy_sfx(it->second);
+      long_jump(e, tl, q);
+      e.l("%s:", disp.c_str());
+      banks = false;
+    }
+    e.l("s_waitcnt lgkmcnt(0)");
+    if (!banks) {
+      e.l("s_load_dwordx8 s[76:83], s[60:61], s62");
+      e.l("s_load_dwordx8 s[84:91], s[60:61], s62 offset:0x20");
       e.l("s_waitcnt lgkmcnt(0)");
-      if (!banks) {
-        e.l("s_load_dwordx8 s[76:83], s[60:61], s62");
-        e.l("s_load_dwordx8 s[84:91], s[60:61], s62 offset:0x20");
-        e.l("s_waitcnt lgkmcnt(0)");
+    }
+    e.l("s_add_u32 s68, s70, s76");
+    e.l("s_addc_u32 s69, s71, 0");
+    e.l("s_setpc_b64 s[68:69]");
+  }
+  // a taken transfer: the core's taken() checks (count limit; diverged: a jump to or
+  // below the lowest waiting pc re-aims OTHER, reaching OTHER goes to the scheduler)
+  void taken_checks() {
+    e.l("s_cmp_ge_u32 s65, s64");
+    e.l("s_cbranch_scc1 %s", xs.c_str());
+    e.l("s_cmp_le_u32 s62, s95");
+    e.l("s_cselect_b32 s63, s95, s63");
+    e.l("s_cmp_ge_u32 s62, s63");
+    e.l("s_cbranch_scc1 %s", xs.c_str());
+  }
+  // The common case of a transfer to pc `to` that starts a compiled run, in one branch:
+  // (taken) the count limit is not reached, and after the re-aim that run stops short of
+  // OTHER -- the jump goes straight there; else the full checks below (go, taken_checks)
+  // run as before. `lim`: the limit is already in s68 (budget ? OTHER : 0) -- a return's
+  // shared prefix, see below.
+  void fast_to(uint32_t to, bool taken, bool lim) {
+    auto it = ix.start.find(to);
+    if (it == ix.start.end()) return;
+    const uint32_t tend = (to + runs[it->second].len - 1) * 32u;
+    const std::string tl = "Lb" + std::to_string(it->second) +
+                           copy_sfx(it->second);
+    if (lim) {
+      e.l("s_cmp_gt_u32 s68, 0x%x", tend);
+    } else if (taken) {
+      if (to == 0) {   // (pc 0 <= LOW always)
+        e.l("s_mov_b32 s63, s95");
+      } else {
+        e.l("s_cmp_ge_u32 s95, 0x%x", to * 32u);   // to <= LOW: re-aim OTHER
+        e.l("s_cselect_b32 s63, s95, s63");
       }
-      e.l("s_add_u32 s68, s70, s76");
-      e.l("s_addc_u32 s69, s71, 0");
-      e.l("s_setpc_b64 s[68:69]");
-    };
-    // a taken transfer: the core's taken() checks (count limit; diverged: a jump to or
-    // below the lowest waiting pc re-aims OTHER, reaching OTHER goes to the scheduler)
-    auto taken_checks = [&]() {
-      e.l("s_cmp_ge_u32 s65, s64");
-      e.l("s_cbranch_scc1 %s", xs.c_str());
+      e.l("s_cmp_lt_u32 s65, s64");
+      e.l("s_cselect_b32 s68, s63, 0");
+      e.l("s_cmp_gt_u32 s68, 0x%x", tend);
+    } else {
+      e.l("s_cmp_gt_u32 s63, 0x%x", tend);
+    }
+    cond_jump(e, tl, "Lf" + K + "_" + std::to_string(nfast++));
+  }
+  void fallthrough(uint32_t cnt) {   // next(): stop at the lowest waiting pc
+    e.gas_add(c_fall);
+    e.l("s_add_u32 s65, s65, 0x%x", cnt);
+    fast_to(fall, false, false);
+    e.l("s_mov_b32 s62, 0x%x", fall * 32u);
+    e.l("s_cmp_ge_u32 s62, s63");
+    e.l("s_cbranch_scc1 %s", xs.c_str());
+    go(fall, preload);
+  }
+
+  // ---- the transfer, by the run's last op
+  bool tail_inlined() {
+    const int64_t inl_f = pl.inl_f[k], inl_post = pl.inl_post[k];
+    const auto fwd_it = pl.plans.find(k);
+    const FwdPlan *fwd = fwd_it != pl.plans.end() ? &fwd_it->second : nullptr;
+    const JitRun &rf = runs[size_t(inl_f)];
+    const uint32_t L = last.w1 & 0xFFFFu, nargs = last.w1 >> 16, nloc = last.w2 & 0xFFFFu;
+    const uint32_t fb = P.global_cells, off = L - fb, n = L - fb, callpc = e.pc;
+    const std::string IK = "i" + K;
+    // the real call's LDS check first: a call that would pass the LDS part of the call
+    // stack leaves before the CALL (the C++ step makes it), as without inlining
+    e.l("v_add_u32_e32 %s, %u, v102", X0, n + 1);
+    e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
+    e.leave_if_t2();
+    const std::vector<uint8_t> dead = dead_zeros(P, rf);
+    // (labels apart from every real run's; counted before the callee: the caller's run)
+    Em ei = e.inlined(e.run + uint32_t(runs.size()), off, r.cnt);
+    for (uint32_t q = 0; q < nloc; q++)
+      if (dead.empty() || !dead[fb + nargs + q]) ei.l("v_mov_b32 %s, 0", ei.v(fb + nargs + q));
+    std::vector<int> lead2;
+    const std::vector<MemGroup> groups2 = jit_groups(P, rf, &lead2);
+    const size_t body2 = ei.o.size();
+    const bool fc = fwd && var == 1;   // the forwarding copy: the callee's loads from F
+    int64_t renamed = -1;              // the stack cell computed into a word's VGPR
+    std::vector<std::pair<uint32_t, uint32_t>> deferred;   // (cell, VGPR) read, then written
+    const std::vector<LoadBatch> batches2 = kn.load_batch && !fc ? load_batches(P, rf, rf.len - 1, lead2)
+                                                            : std::vector<LoadBatch>();
+    size_t nb2 = 0;
+    for (uint32_t i = 0; i + 1 < rf.len; i++) {
+      if (nb2 < batches2.size() && batches2[nb2].i0 == i) {
+        const LoadBatch &b = batches2[nb2++];
+        emit_batch(ei, P, rf.pc, b, groups2, lead2);
+        for (uint32_t k = b.i0; k < b.i1; k++) {
+          ei.done += (P.code[rf.pc + k].w0 >> 16) & 0xFFu;
+          if (fwd && fwd->copy_now[k]) {
+            const uint32_t c = P.code[rf.pc + k].w2 & 0xFFFFu;
+            ei.sync({c});
+            ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fwd->addr[k])), ei.v(c));
+          }
+        }
+        i = b.i1 - 1;
+        continue;
+      }
+      const DInstr &I = P.code[rf.pc + i];
+      ei.pc = rf.pc + i;
+      ei.group = lead2[i] >= 0 ? &groups2[size_t(lead2[i])] : nullptr;
+      const int64_t fa = fwd ? fwd->addr[i] : -1;
+      if (fa >= 0 && fc && op_of(I) == OP_LD32) {
+        // (a group that also stores still computes its base: its stores use it)
+        if (ei.group && ei.group->store_end) group_base(ei, *ei.group);
+        ei.group = nullptr;
+        const uint32_t c = I.w2 & 0xFFFFu;
+        ei.sync({c});
+        if (kn.fwd_alias) ei.amap[c] = fwd->freg.at(uint32_t(fa));
+        else ei.l("v_mov_b32 %s, v%u", ei.v(c), fwd->freg.at(uint32_t(fa)));
+        ei.done += (I.w0 >> 16) & 0xFFu;
+        continue;
+      }
+      if (!ei.amap.empty() && !(fa >= 0 && op_of(I) == OP_ST32 && kn.fwd_store)) {
+        // an aliased cell this instruction writes gets its own register back first if
+        // the instruction also reads it (else the alias just ends); anything but a plain
+        // 32-bit op (which might leave, or names register pairs) gets every cell back
+        std::vector<uint32_t> w;
+        const bool ex = written_exact(I, &w);
+        std::vector<uint32_t> cells;
+        for (const auto &kv : ei.amap) cells.push_back(kv.first);
+        for (uint32_t x : cells) {
+          const bool wr = std::find(w.begin(), w.end(), x) != w.end();
+          const bool rd = (I.w1 & 0xFFFFu) == x || (I.w1 >> 16) == x || (I.w2 >> 16) == x ||
+                          (op_of(I) == OP_I32_ADD3_XROTR_I && (I.w3 & 0xFFFFu) == x);
+          size_t shared = 0;
+          for (const auto &kv : ei.amap) shared += kv.second == ei.amap[x];
+          if (ex && wr && rd && shared == 1) deferred.push_back({x, ei.amap[x]});
+          else if (!ex || (wr && rd)) ei.materialize(x);
+          else if (wr) ei.amap.erase(x);
+        }
+      }
+      if (fa >= 0 && op_of(I) == OP_ST32 && kn.fwd_store) {
+        // the word goes to its VGPR first and is stored from there: the stack cell that
+        // held it is free at once for the next value (no wait for the store's data read)
+        const std::string fr = "v" + std::to_string(fwd->freg.at(uint32_t(fa)));
+        ei.before_write(fwd->freg.at(uint32_t(fa)));
+        if (renamed != int64_t(I.w1 >> 16)) {
+          ei.sync({I.w1 >> 16});
+          ei.l("v_mov_b32 %s, %s", fr.c_str(), ei.v(I.w1 >> 16));
+        }
+        renamed = -1;
+        if (fc) {   // (the first trip checked these constant addresses, raised the mark)
+          if (ei.group) group_base(ei, *ei.group);
+          ei.group = nullptr;
+        }
+        emit_store(ei, OP_ST32, I.w1 & 0xFFFFu, I.w1 >> 16, I.w3, fr.c_str());
+        ei.done += (I.w0 >> 16) & 0xFFu;
+        continue;
+      }
+      // a stack cell computed only to be stored as a forwarded word (it is dead after
+      // the store pops it): computed straight into the word's VGPR
+      renamed = -1;
+      // (only in the copy: there the store cannot leave, which would need the cell)
+      if (fc && kn.fwd_store && i + 2 < rf.len && fwd->addr[i + 1] >= 0 &&
+          op_of(P.code[rf.pc + i + 1]) == OP_ST32) {
+        const uint32_t y = P.code[rf.pc + i + 1].w1 >> 16;
+        std::vector<uint32_t> w;
+        written_exact(I, &w);
+        const bool srcs = (I.w1 & 0xFFFFu) != y && (I.w1 >> 16) != y && (I.w2 >> 16) != y &&
+                          (op_of(I) != OP_I32_ADD3_XROTR_I || (I.w3 & 0xFFFFu) != y);
+        if (y >= fb + nargs + nloc && w.size() == 1 && w[0] == y && srcs &&
+            op_of(I) != OP_LD32 && !mem_bytes(op_of(I))) {
+          ei.sync({y});
+          ei.before_write(fwd->freg.at(uint32_t(fwd->addr[i + 1])));
+          ei.alias_cell = y;
+          ei.alias_reg = fwd->freg.at(uint32_t(fwd->addr[i + 1]));
+          renamed = y;
+        }
+      }
+      const size_t mark = ei.o.size();
+      if (!emit(ei, I)) return false;
+      ei.alias_cell = -1;
+      // A cell read through its alias and written by this instruction: the instruction
+      // read the word's VGPR; its first line that writes the VGPR writes the cell's own
+      // register instead, and later lines read that (else: the cell back first, again)
+      for (const auto &dx : deferred) {
+        const std::string fv = "v" + std::to_string(dx.second);
+        const std::string rv = "v" + std::to_string(128 + ei.sc(dx.first));
+        std::string out;
+        bool written = false;
+        for (size_t at = mark; at < ei.o.size();) {
+          size_t nl = ei.o.find('\n', at);
+          std::string ln = ei.o.substr(at, nl - at);
+          at = nl + 1;
+          const size_t sp = ln.find(' ');
+          if (!written && ln.compare(0, 2, "v_") == 0 && sp != std::string::npos &&
+              ln.compare(sp + 1, fv.size(), fv) == 0 &&
+              (sp + 1 + fv.size() == ln.size() || ln[sp + 1 + fv.size()] == ',')) {
+            ln = ln.substr(0, sp + 1) + rv + ln.substr(sp + 1 + fv.size());
+            written = true;
+          } else if (written) {
+            for (size_t q = ln.find(fv); q != std::string::npos; q = ln.find(fv, q + rv.size())) {
+              const size_t e2 = q + fv.size();
+              if ((q == 0 || !isalnum((unsigned char)ln[q - 1])) &&
+                  (e2 == ln.size() || !isdigit((unsigned char)ln[e2])))
+                ln = ln.substr(0, q) + rv + ln.substr(e2);
+            }
+          }
+          out += ln + "\n";
+        }
+        if (written) {
+          ei.o = ei.o.substr(0, mark) + out;
+          ei.amap.erase(dx.first);
+        } else {   // (not expected: every exact write names the cell's register)
+          ei.o.resize(mark);
+          ei.materialize(dx.first);
+          if (!emit(ei, I)) return false;
+        }
+      }
+      deferred.clear();
+      if (fa >= 0 && op_of(I) == OP_ST32) {   // (WB_FWD_STORE=0: copied after the store)
+        ei.before_write(fwd->freg.at(uint32_t(fa)));
+        ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fa)), ei.v(I.w1 >> 16));
+      }
+      if (fa >= 0 && fwd->copy_now[i]) {
+        ei.sync({I.w2 & 0xFFFFu});
+        ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fa)), ei.v(I.w2 & 0xFFFFu));
+      }
+      ei.done += (I.w0 >> 16) & 0xFFu;
+    }
+    ei.drain();
+    if (fwd && !fc)
+      for (const auto &fc2 : fwd->end_copy) ei.l("v_mov_b32 v%u, v%u", fc2.first, 128 + fc2.second);
+    ei.group = nullptr;
+    if (kn.jit_sched) ei.o = ei.o.substr(0, body2) + schedule(ei.o.substr(body2), kn);
+    // the return: results (shifted cells a..) to L.., every instruction counted, on after
+    // the caller's POST_CALL (its run's banks as that run would have loaded them)
+    const DInstr &rt = P.code[rf.pc + rf.len - 1];
+    const uint32_t ra = rt.w1 & 0xFFFFu, nres = rt.w1 >> 16;
+    for (uint32_t q = 0; q < nres; q++)
+      ei.l("v_mov_b32 v%u, %s", 128 + L + q, ei.v(ra + q));
+    ei.amap.clear();   // (the callee's cells are dead once its results are out)
+    ei.l("s_add_u32 s65, s65, 0x%x", r.cnt + rf.cnt);
+    {
+      const JitRun &rp = runs[size_t(inl_post)];
+      const DInstr &pl = P.code[rp.pc + rp.len - 1];
+      const uint16_t plo = op_of(pl);
+      const uint32_t ptgt = (plo == OP_CALL || is_branch_op(plo)) ? pl.w3 : 0;
+      const uint32_t ppre = plo == OP_CALL ? ptgt : rp.pc + rp.len;
+      if (plo != OP_RET && plo != OP_JMP && plo != OP_BR_TABLE && !ix.has(ppre)) {
+        ei.l("s_waitcnt lgkmcnt(0)");
+        ei.l("s_mov_b32 s68, 0x%x", ppre * 32u);
+        ei.l("s_load_dwordx8 s[76:83], s[60:61], s68");
+        ei.l("s_load_dwordx8 s[84:91], s[60:61], s68 offset:0x20");
+      }
+    }
+    ei.l("s_mov_b32 s62, 0x%x", (callpc + 1) * 32u);
+    long_jump(ei, "Lpa" + std::to_string(inl_post) + (fwd ? "p" : ""), "Lpq" + IK);
+    // leaves inside the callee: make the call real first
+    std::string deopt;
+    {
+      Em d(t);
+      d.l("s_waitcnt vmcnt(0)");   // (the callee's loads in flight land before the moves)
+      d.l("v_lshl_add_u32 %s, v102, 8, v103", X1);
+      for (uint32_t q = 0; q < n; q++) d.l("ds_write_b32 %s, v%u offset:%u", X1, 128 + fb + q, q * 256u);
+      d.l("v_mov_b32 %s, 0x%x", Y1, ((callpc + 1) & 0xFFFFFu) | (L << 20));
+      d.l("ds_write_b32 %s, %s offset:%u", X1, Y1, n * 256u);
+      d.l("v_add_u32_e32 v102, %u, v102", n + 1);
+      for (uint32_t c = fb; c < P.total_cells(); c++) d.l("v_mov_b32 v%u, v%u", 128 + c, 128 + c + off);
+      deopt = d.o;
+    }
+    ei.o += ei.tail;
+    for (const auto &st : ei.stubs) {
+      ei.o += st.lab + ":\n" + deopt;
+      ei.l("s_mov_b32 s62, 0x%x", st.pc * 32u);
+      ei.l("s_add_u32 s65, s65, 0x%x", st.done);
+      ei.l("s_setpc_b64 s[70:71]");
+    }
+    // the callee's code follows the caller's (falls through into it; its block counts
+    // the caller's run)
+    e.l("Li%s:", IK.c_str());
+    e.o += ei.o;
+    return true;
+  }
+  void tail_tail_call() {
+    std::vector<uint8_t> dead;
+    if (ix.has(tgt)) dead = dead_zeros(P, runs[ix.at(tgt)]);
+    emit_tail_call(e, last, dead.empty() ? nullptr : &dead);
+    e.gas_add(c_fall);
+    e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+    fast_to(tgt, true, false);
+    e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
+    taken_checks();
+    go(tgt, preload);
+  }
+  void tail_call() {
+    std::vector<uint8_t> dead;
+    if (ix.has(tgt)) dead = dead_zeros(P, runs[ix.at(tgt)]);
+    emit_call(e, last, e.pc, dead.empty() ? nullptr : &dead);
+    e.gas_add(c_fall);
+    e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+    fast_to(tgt, true, false);
+    e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
+    taken_checks();
+    go(tgt, preload);
+  }
+  void tail_ret() {
+    // a return's likely targets: the instruction after each direct call of its function
+    std::vector<uint32_t> sites;
+    const int64_t f = ix.func_of(e.pc);
+    const auto rs_it = f >= 0 ? pl.ret_sites.find(uint32_t(f)) : pl.ret_sites.end();
+    if (rs_it != pl.ret_sites.end())
+      for (uint32_t rs : rs_it->second)
+        if (ix.has(rs) && sites.size() < 6) sites.push_back(rs);
+    // the first two sites' return records are constants: a group whose lanes all hold one
+    // of them goes straight to Lrk<K>_<q> (below)
+    std::vector<std::pair<uint32_t, std::string>> known;
+    for (size_t q = 0; q < sites.size() && q < 2 && !cost; q++) {
+      const DInstr &cl = P.code[sites[q] - 1];
+      const uint32_t L = cl.w1 & 0xFFFFu;
+      if (op_of(cl) == OP_CALL && L < 4096)
+        known.push_back({(sites[q] & 0xFFFFFu) | (L << 20), "Lrk" + K + "_" + std::to_string(q)});
+    }
+    const std::string rout = emit_ret(e, last, (sx & 2) ? "Lrs" + K : std::string(), known);
+    if (sx & 2) {
+      // lanes returning to different places: each records its return pc and count
+      // (unless one leaves the entry function: the C++ step finishes those) and the
+      // scheduler picks who goes on
+      const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
+      Em x(t);
+      x.l("Lrs%s:", K.c_str());
+      x.l("v_and_b32_e32 %s, 0xfffff, %s", X0, Y1);
+      x.l("v_cmp_eq_u32_e32 vcc, 0xfffff, %s", X0);
+      x.l("s_and_b64 vcc, vcc, exec");
+      x.l("s_cbranch_vccnz %s", rout.c_str());
+      x.l("v_subrev_u32_e32 v102, 1, v102");
+      for (uint32_t q = 0; q < nres; q++)
+        if (a != fb) x.l("v_mov_b32 %s, %s", x.V(fb + q).c_str(), x.V(a + q).c_str());
+      x.l("v_mov_b32 %s, %s", VPC, X0);
+      x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+      flush(x);
+      long_jump(x, "Lsched", "Lrq" + K);
+      extra += x.o;
+    }
+    e.gas_add(c_fall);
+    e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+    // straight into the code after a known call site of this function, else dispatch
+    // the fast way: re-aim, s68 = the limit (budget ? OTHER : 0), then per known site
+    // one compare against the site's run end (fast_to)
+    if (!sites.empty()) {
       e.l("s_cmp_le_u32 s62, s95");
       e.l("s_cselect_b32 s63, s95, s63");
-      e.l("s_cmp_ge_u32 s62, s63");
-      e.l("s_cbranch_scc1 %s", xs.c_str());
-    };
-    // The common case of a transfer to pc `to` that starts a compiled run, in one branch:
-    // (taken) the count limit is not reached, and after the re-aim that run stops short of
-    // OTHER -- the jump goes straight there; else the full checks below (go, taken_checks)
-    // run as before. `lim`: the limit is already in s68 (budget ? OTHER : 0) -- a return's
-    // shared prefix, see below.
-    int nfast = 0;
-    auto fast_to = [&](uint32_t to, bool taken, bool lim) {
-      auto it = start.find(to);
-      if (it == start.end()) return;
-      const uint32_t tend = (to + runs[it->second].len - 1) * 32u;
-      const std::string tl = "Lb" + std::to_string(it->second) +
-                             (var == 2 && loop_of.count(k) && loop_of[k] == it->second ? "c" : "");
-      if (lim) {
-        e.l("s_cmp_gt_u32 s68, 0x%x", tend);
-      } else if (taken) {
-        if (to == 0) {   // (pc 0 <= LOW always)
-          e.l("s_mov_b32 s63, s95");
-        } else {
-          e.l("s_cmp_ge_u32 s95, 0x%x", to * 32u);   // to <= LOW: re-aim OTHER
-          e.l("s_cselect_b32 s63, s95, s63");
-        }
-        e.l("s_cmp_lt_u32 s65, s64");
-        e.l("s_cselect_b32 s68, s63, 0");
-        e.l("s_cmp_gt_u32 s68, 0x%x", tend);
-      } else {
-        e.l("s_cmp_gt_u32 s63, 0x%x", tend);
+      e.l("s_cmp_lt_u32 s65, s64");
+      e.l("s_cselect_b32 s68, s63, 0");
+      // the limit clears every site's run (converged: always): straight to the site
+      uint32_t maxend = 0;
+      std::vector<std::string> tls;
+      for (uint32_t rs : sites) {
+        const size_t ri = ix.at(rs);
+        maxend = std::max(maxend, (rs + runs[ri].len - 1) * 32u);
+        tls.push_back("Lb" + std::to_string(ri) + copy_sfx(ri));
       }
-      cond_jump(e, tl, "Lf" + K + "_" + std::to_string(nfast++));
-    };
-    auto fallthrough = [&](uint32_t cnt) {   // next(): stop at the lowest waiting pc
-      e.gas_add(c_fall);
-      e.l("s_add_u32 s65, s65, 0x%x", cnt);
-      fast_to(fall, false, false);
-      e.l("s_mov_b32 s62, 0x%x", fall * 32u);
-      e.l("s_cmp_ge_u32 s62, s63");
-      e.l("s_cbranch_scc1 %s", xs.c_str());
-      go(fall, preload);
-    };
-    int64_t inl_f = -1, inl_post = -1;
-    inline_of(k, &inl_f, &inl_post);
-    const FwdPlan *fwd = plans.count(k) ? &plans[k] : nullptr;
-    if (inl_f >= 0) {
-      const JitRun &rf = runs[size_t(inl_f)];
-      const uint32_t L = last.w1 & 0xFFFFu, nargs = last.w1 >> 16, nloc = last.w2 & 0xFFFFu;
-      const uint32_t fb = P.global_cells, off = L - fb, n = L - fb, callpc = e.pc;
-      const std::string IK = "i" + K;
-      // the real call's LDS check first: a call that would pass the LDS part of the call
-      // stack leaves before the CALL (the C++ step makes it), as without inlining
-      e.l("v_add_u32_e32 %s, %u, v102", X0, n + 1);
-      e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
-      e.leave_if_t2();
-      const std::vector<uint8_t> dead = dead_zeros(P, rf);
-      Em ei;
-      ei.g = glog;
-      ei.run = e.run + uint32_t(runs.size());   // (labels apart from every real run's)
-      ei.fb = fb;
-      ei.prog = &P;
-      ei.shift = off;
-      ei.nanobs = e.nanobs;
-      ei.done = r.cnt;                      // counted before the callee: the caller's run
-      for (uint32_t q = 0; q < nloc; q++)
-        if (dead.empty() || !dead[fb + nargs + q]) ei.l("v_mov_b32 %s, 0", ei.v(fb + nargs + q));
-      std::vector<int> lead2;
-      const std::vector<MemGroup> groups2 = jit_groups(P, rf, &lead2);
-      const size_t body2 = ei.o.size();
-      const bool fc = fwd && var == 1;   // the forwarding copy: the callee's loads from F
-      int64_t renamed = -1;              // the stack cell computed into a word's VGPR
-      std::vector<std::pair<uint32_t, uint32_t>> deferred;   // (cell, VGPR) read, then written
-      const std::vector<LoadBatch> batches2 = batching && !fc ? load_batches(P, rf, rf.len - 1, lead2)
-                                                              : std::vector<LoadBatch>();
-      size_t nb2 = 0;
-      for (uint32_t i = 0; i + 1 < rf.len; i++) {
-        if (nb2 < batches2.size() && batches2[nb2].i0 == i) {
-          const LoadBatch &b = batches2[nb2++];
-          emit_batch(ei, P, rf.pc, b, groups2, lead2);
-          for (uint32_t k = b.i0; k < b.i1; k++) {
-            ei.done += (P.code[rf.pc + k].w0 >> 16) & 0xFFu;
-            if (fwd && fwd->copy_now[k]) {
-              const uint32_t c = P.code[rf.pc + k].w2 & 0xFFFFu;
-              ei.sync({c});
-              ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fwd->addr[k])), ei.v(c));
-            }
-          }
-          i = b.i1 - 1;
-          continue;
-        }
-        const DInstr &I = P.code[rf.pc + i];
-        ei.pc = rf.pc + i;
-        ei.group = lead2[i] >= 0 ? &groups2[size_t(lead2[i])] : nullptr;
-        const int64_t fa = fwd ? fwd->addr[i] : -1;
-        if (fa >= 0 && fc && op_of(I) == OP_LD32) {
-          // (a group that also stores still computes its base: its stores use it)
-          if (ei.group && ei.group->store_end) group_base(ei, *ei.group);
-          ei.group = nullptr;
-          const uint32_t c = I.w2 & 0xFFFFu;
-          ei.sync({c});
-          if (fwd_alias) ei.amap[c] = fwd->freg.at(uint32_t(fa));
-          else ei.l("v_mov_b32 %s, v%u", ei.v(c), fwd->freg.at(uint32_t(fa)));
-          ei.done += (I.w0 >> 16) & 0xFFu;
-          continue;
-        }
-        if (!ei.amap.empty() && !(fa >= 0 && op_of(I) == OP_ST32 && fwd_store)) {
-          // an aliased cell this instruction writes gets its own register back first if
-          // the instruction also reads it (else the alias just ends); anything but a plain
-          // 32-bit op (which might leave, or names register pairs) gets every cell back
-          std::vector<uint32_t> w;
-          const bool ex = written_exact(I, &w);
-          std::vector<uint32_t> cells;
-          for (const auto &kv : ei.amap) cells.push_back(kv.first);
-          for (uint32_t x : cells) {
-            const bool wr = std::find(w.begin(), w.end(), x) != w.end();
-            const bool rd = (I.w1 & 0xFFFFu) == x || (I.w1 >> 16) == x || (I.w2 >> 16) == x ||
-                            (op_of(I) == OP_I32_ADD3_XROTR_I && (I.w3 & 0xFFFFu) == x);
-            size_t shared = 0;
-            for (const auto &kv : ei.amap) shared += kv.second == ei.amap[x];
-            if (ex && wr && rd && shared == 1) deferred.push_back({x, ei.amap[x]});
-            else if (!ex || (wr && rd)) ei.materialize(x);
-            else if (wr) ei.amap.erase(x);
-          }
-        }
-        if (fa >= 0 && op_of(I) == OP_ST32 && fwd_store) {
-          // the word goes to its VGPR first and is stored from there: the stack cell that
-          // held it is free at once for the next value (no wait for the store's data read)
-          const std::string fr = "v" + std::to_string(fwd->freg.at(uint32_t(fa)));
-          ei.before_write(fwd->freg.at(uint32_t(fa)));
-          if (renamed != int64_t(I.w1 >> 16)) {
-            ei.sync({I.w1 >> 16});
-            ei.l("v_mov_b32 %s, %s", fr.c_str(), ei.v(I.w1 >> 16));
-          }
-          renamed = -1;
-          if (fc) {   // (the first trip checked these constant addresses, raised the mark)
-            if (ei.group) group_base(ei, *ei.group);
-            ei.group = nullptr;
-          }
-          emit_store(ei, OP_ST32, I.w1 & 0xFFFFu, I.w1 >> 16, I.w3, fr.c_str());
-          ei.done += (I.w0 >> 16) & 0xFFu;
-          continue;
-        }
-        // a stack cell computed only to be stored as a forwarded word (it is dead after
-        // the store pops it): computed straight into the word's VGPR
-        renamed = -1;
-        // (only in the copy: there the store cannot leave, which would need the cell)
-        if (fc && fwd_store && i + 2 < rf.len && fwd->addr[i + 1] >= 0 &&
-            op_of(P.code[rf.pc + i + 1]) == OP_ST32) {
-          const uint32_t y = P.code[rf.pc + i + 1].w1 >> 16;
-          std::vector<uint32_t> w;
-          written_exact(I, &w);
-          const bool srcs = (I.w1 & 0xFFFFu) != y && (I.w1 >> 16) != y && (I.w2 >> 16) != y &&
-                            (op_of(I) != OP_I32_ADD3_XROTR_I || (I.w3 & 0xFFFFu) != y);
-          if (y >= fb + nargs + nloc && w.size() == 1 && w[0] == y && srcs &&
-              op_of(I) != OP_LD32 && !mem_bytes(op_of(I))) {
-            ei.sync({y});
-            ei.before_write(fwd->freg.at(uint32_t(fwd->addr[i + 1])));
-            ei.alias_cell = y;
-            ei.alias_reg = fwd->freg.at(uint32_t(fwd->addr[i + 1]));
-            renamed = y;
-          }
-        }
-        const size_t mark = ei.o.size();
-        if (!emit(ei, I)) return "";
-        ei.alias_cell = -1;
-        // A cell read through its alias and written by this instruction: the instruction
-        // read the word's VGPR; its first line that writes the VGPR writes the cell's own
-        // register instead, and later lines read that (else: the cell back first, again)
-        for (const auto &dx : deferred) {
-          const std::string fv = "v" + std::to_string(dx.second);
-          const std::string rv = "v" + std::to_string(128 + ei.sc(dx.first));
-          std::string out;
-          bool written = false;
-          for (size_t at = mark; at < ei.o.size();) {
-            size_t nl = ei.o.find('\n', at);
-            std::string ln = ei.o.substr(at, nl - at);
-            at = nl + 1;
-            const size_t sp = ln.find(' ');
-            if (!written && ln.compare(0, 2, "v_") == 0 && sp != std::string::npos &&
-                ln.compare(sp + 1, fv.size(), fv) == 0 &&
-                (sp + 1 + fv.size() == ln.size() || ln[sp + 1 + fv.size()] == ',')) {
-              ln = ln.substr(0, sp + 1) + rv + ln.substr(sp + 1 + fv.size());
-              written = true;
-            } else if (written) {
-              for (size_t q = ln.find(fv); q != std::string::npos; q = ln.find(fv, q + rv.size())) {
-                const size_t e2 = q + fv.size();
-                if ((q == 0 || !isalnum((unsigned char)ln[q - 1])) &&
-                    (e2 == ln.size() || !isdigit((unsigned char)ln[e2])))
-                  ln = ln.substr(0, q) + rv + ln.substr(e2);
-              }
-            }
-            out += ln + "\n";
-          }
-          if (written) {
-            ei.o = ei.o.substr(0, mark) + out;
-            ei.amap.erase(dx.first);
-          } else {   // (not expected: every exact write names the cell's register)
-            ei.o.resize(mark);
-            ei.materialize(dx.first);
-            if (!emit(ei, I)) return "";
-          }
-        }
-        deferred.clear();
-        if (fa >= 0 && op_of(I) == OP_ST32) {   // (WB_FWD_STORE=0: copied after the store)
-          ei.before_write(fwd->freg.at(uint32_t(fa)));
-          ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fa)), ei.v(I.w1 >> 16));
-        }
-        if (fa >= 0 && fwd->copy_now[i]) {
-          ei.sync({I.w2 & 0xFFFFu});
-          ei.l("v_mov_b32 v%u, %s", fwd->freg.at(uint32_t(fa)), ei.v(I.w2 & 0xFFFFu));
-        }
-        ei.done += (I.w0 >> 16) & 0xFFu;
-      }
-      ei.drain();
-      if (fwd && !fc)
-        for (const auto &fc2 : fwd->end_copy) ei.l("v_mov_b32 v%u, v%u", fc2.first, 128 + fc2.second);
-      ei.group = nullptr;
-      if (sched) ei.o = ei.o.substr(0, body2) + schedule(ei.o.substr(body2));
-      // the return: results (shifted cells a..) to L.., every instruction counted, on after
-      // the caller's POST_CALL (its run's banks as that run would have loaded them)
-      const DInstr &rt = P.code[rf.pc + rf.len - 1];
-      const uint32_t ra = rt.w1 & 0xFFFFu, nres = rt.w1 >> 16;
-      for (uint32_t q = 0; q < nres; q++)
-        ei.l("v_mov_b32 v%u, %s", 128 + L + q, ei.v(ra + q));
-      ei.amap.clear();   // (the callee's cells are dead once its results are out)
-      ei.l("s_add_u32 s65, s65, 0x%x", r.cnt + rf.cnt);
-      {
-        const JitRun &rp = runs[size_t(inl_post)];
-        const DInstr &pl = P.code[rp.pc + rp.len - 1];
-        const uint16_t plo = op_of(pl);
-        const uint32_t ptgt = (plo == OP_CALL || is_branch_op(plo)) ? pl.w3 : 0;
-        const uint32_t ppre = plo == OP_CALL ? ptgt : rp.pc + rp.len;
-        if (plo != OP_RET && plo != OP_JMP && plo != OP_BR_TABLE && !start.count(ppre)) {
-          ei.l("s_waitcnt lgkmcnt(0)");
-          ei.l("s_mov_b32 s68, 0x%x", ppre * 32u);
-          ei.l("s_load_dwordx8 s[76:83], s[60:61], s68");
-          ei.l("s_load_dwordx8 s[84:91], s[60:61], s68 offset:0x20");
-        }
-      }
-      ei.l("s_mov_b32 s62, 0x%x", (callpc + 1) * 32u);
-      long_jump(ei, "Lpa" + std::to_string(inl_post) + (fwd ? "p" : ""), "Lpq" + IK);
-      // leaves inside the callee: make the call real first
-      std::string deopt;
-      {
-        Em d;
-        d.l("s_waitcnt vmcnt(0)");   // (the callee's loads in flight land before the moves)
-        d.l("v_lshl_add_u32 %s, v102, 8, v103", X1);
-        for (uint32_t q = 0; q < n; q++) d.l("ds_write_b32 %s, v%u offset:%u", X1, 128 + fb + q, q * 256u);
-        d.l("v_mov_b32 %s, 0x%x", Y1, ((callpc + 1) & 0xFFFFFu) | (L << 20));
-        d.l("ds_write_b32 %s, %s offset:%u", X1, Y1, n * 256u);
-        d.l("v_add_u32_e32 v102, %u, v102", n + 1);
-        for (uint32_t c = fb; c < P.total_cells(); c++) d.l("v_mov_b32 v%u, v%u", 128 + c, 128 + c + off);
-        deopt = d.o;
-      }
-      ei.o += ei.tail;
-      for (const auto &st : ei.stubs) {
-        ei.o += st.lab + ":\n" + deopt;
-        ei.l("s_mov_b32 s62, 0x%x", st.pc * 32u);
-        ei.l("s_add_u32 s65, s65, 0x%x", st.done);
-        ei.l("s_setpc_b64 s[70:71]");
-      }
-      // the callee's code follows the caller's (falls through into it; its block counts
-      // the caller's run)
-      e.l("Li%s:", IK.c_str());
-      e.o += ei.o;
-    } else if (lop == OP_TAIL_CALL) {
-      std::vector<uint8_t> dead;
-      if (start.count(tgt)) dead = dead_zeros(P, runs[start[tgt]]);
-      emit_tail_call(e, last, dead.empty() ? nullptr : &dead);
-      e.gas_add(c_fall);
-      e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-      fast_to(tgt, true, false);
-      e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
-      taken_checks();
-      go(tgt, preload);
-    } else if (lop == OP_CALL) {
-      std::vector<uint8_t> dead;
-      if (start.count(tgt)) dead = dead_zeros(P, runs[start[tgt]]);
-      emit_call(e, last, e.pc, dead.empty() ? nullptr : &dead);
-      e.gas_add(c_fall);
-      e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-      fast_to(tgt, true, false);
-      e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
-      taken_checks();
-      go(tgt, preload);
-    } else if (lop == OP_RET) {
-      // a return's likely targets: the instruction after each direct call of its function
-      std::vector<uint32_t> sites;
-      const int64_t f = func_of(e.pc);
-      if (f >= 0)
-        for (uint32_t rs : ret_sites[uint32_t(f)])
-          if (start.count(rs) && sites.size() < 6) sites.push_back(rs);
-      // the first two sites' return records are constants: a group whose lanes all hold one
-      // of them goes straight to Lrk<K>_<q> (below)
-      std::vector<std::pair<uint32_t, std::string>> known;
-      for (size_t q = 0; q < sites.size() && q < 2 && !cost; q++) {
-        const DInstr &cl = P.code[sites[q] - 1];
-        const uint32_t L = cl.w1 & 0xFFFFu;
-        if (op_of(cl) == OP_CALL && L < 4096)
-          known.push_back({(sites[q] & 0xFFFFFu) | (L << 20), "Lrk" + K + "_" + std::to_string(q)});
-      }
-      const std::string rout = emit_ret(e, last, (sx & 2) ? "Lrs" + K : std::string(), known);
-      if (sx & 2) {
-        // lanes returning to different places: each records its return pc and count
-        // (unless one leaves the entry function: the C++ step finishes those) and the
-        // scheduler picks who goes on
-        const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
-        Em x;
-        x.l("Lrs%s:", K.c_str());
-        x.l("v_and_b32_e32 %s, 0xfffff, %s", X0, Y1);
-        x.l("v_cmp_eq_u32_e32 vcc, 0xfffff, %s", X0);
-        x.l("s_and_b64 vcc, vcc, exec");
-        x.l("s_cbranch_vccnz %s", rout.c_str());
-        x.l("v_subrev_u32_e32 v102, 1, v102");
-        for (uint32_t q = 0; q < nres; q++)
-          if (a != fb) x.l("v_mov_b32 %s, %s", x.V(fb + q).c_str(), x.V(a + q).c_str());
-        x.l("v_mov_b32 %s, %s", VPC, X0);
-        x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-        flush(x);
-        long_jump(x, "Lsched", "Lrq" + K);
-        extra += x.o;
-      }
-      e.gas_add(c_fall);
-      e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-      // straight into the code after a known call site of this function, else dispatch
-      // the fast way: re-aim, s68 = the limit (budget ? OTHER : 0), then per known site
-      // one compare against the site's run end (fast_to)
-      if (!sites.empty()) {
-        e.l("s_cmp_le_u32 s62, s95");
-        e.l("s_cselect_b32 s63, s95, s63");
-        e.l("s_cmp_lt_u32 s65, s64");
-        e.l("s_cselect_b32 s68, s63, 0");
-        // the limit clears every site's run (converged: always): straight to the site
-        uint32_t maxend = 0;
-        std::vector<std::string> tls;
-        for (uint32_t rs : sites) {
-          const size_t ri = start[rs];
-          maxend = std::max(maxend, (rs + runs[ri].len - 1) * 32u);
-          tls.push_back("Lb" + std::to_string(ri) + (var == 2 && loop_of.count(k) && loop_of[k] == ri ? "c" : ""));
-        }
-        e.l("s_cmp_gt_u32 s68, 0x%x", maxend);
-        e.l("s_cbranch_scc0 Lrg%s", K.c_str());
-        for (size_t q = 0; q < sites.size(); q++) {
-          e.l("s_cmp_eq_u32 s62, 0x%x", sites[q] * 32u);
-          cond_jump(e, tls[q], "Lrj" + K + "_" + std::to_string(q));
-        }
-        e.l("Lrg%s:", K.c_str());
-        for (size_t q = 0; q < sites.size(); q++) {
-          e.l("s_cmp_eq_u32 s62, 0x%x", sites[q] * 32u);
-          e.l("s_cbranch_scc1 Lrf%s_%zu", K.c_str(), q);
-        }
-      }
-      taken_checks();
+      e.l("s_cmp_gt_u32 s68, 0x%x", maxend);
+      e.l("s_cbranch_scc0 Lrg%s", K.c_str());
       for (size_t q = 0; q < sites.size(); q++) {
         e.l("s_cmp_eq_u32 s62, 0x%x", sites[q] * 32u);
-        e.l("s_cbranch_scc1 Lrt%s_%zu", K.c_str(), q);
+        cond_jump(e, tls[q], "Lrj" + K + "_" + std::to_string(q));
       }
-      go(~0u, false);
+      e.l("Lrg%s:", K.c_str());
       for (size_t q = 0; q < sites.size(); q++) {
-        e.l("Lrf%s_%zu:", K.c_str(), q);
-        fast_to(sites[q], true, true);
-        taken_checks();
-        e.l("Lrt%s_%zu:", K.c_str(), q);
-        go(sites[q], false);
+        e.l("s_cmp_eq_u32 s62, 0x%x", sites[q] * 32u);
+        e.l("s_cbranch_scc1 Lrf%s_%zu", K.c_str(), q);
       }
-      // every lane returns to known site q: pop, results, then the transfer's checks
-      for (size_t q = 0; q < known.size(); q++) {
-        const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
-        e.l("%s:", known[q].second.c_str());
-        e.l("v_subrev_u32_e32 v102, 1, v102");
-        for (uint32_t c = 0; c < nres; c++)
-          if (a != fb) e.l("v_mov_b32 %s, %s", e.V(fb + c).c_str(), e.V(a + c).c_str());
-        e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-        fast_to(sites[q], true, false);
-        e.l("s_mov_b32 s62, 0x%x", sites[q] * 32u);
-        taken_checks();
-        go(sites[q], false);
+    }
+    taken_checks();
+    for (size_t q = 0; q < sites.size(); q++) {
+      e.l("s_cmp_eq_u32 s62, 0x%x", sites[q] * 32u);
+      e.l("s_cbranch_scc1 Lrt%s_%zu", K.c_str(), q);
+    }
+    go(~0u, false);
+    for (size_t q = 0; q < sites.size(); q++) {
+      e.l("Lrf%s_%zu:", K.c_str(), q);
+      fast_to(sites[q], true, true);
+      taken_checks();
+      e.l("Lrt%s_%zu:", K.c_str(), q);
+      go(sites[q], false);
+    }
+    // every lane returns to known site q: pop, results, then the transfer's checks
+    for (size_t q = 0; q < known.size(); q++) {
+      const uint32_t a = last.w1 & 0xFFFFu, nres = last.w1 >> 16, fb = e.fb;
+      e.l("%s:", known[q].second.c_str());
+      e.l("v_subrev_u32_e32 v102, 1, v102");
+      for (uint32_t c = 0; c < nres; c++)
+        if (a != fb) e.l("v_mov_b32 %s, %s", e.V(fb + c).c_str(), e.V(a + c).c_str());
+      e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+      fast_to(sites[q], true, false);
+      e.l("s_mov_b32 s62, 0x%x", sites[q] * 32u);
+      taken_checks();
+      go(sites[q], false);
+    }
+  }
+  void tail_br_table() {
+    emit_br_table(e, last);
+    // every lane to the same entry: jump there (count + that entry's correction);
+    // else (SIMT) each lane records its target and count and the scheduler picks, or
+    // (no SIMT) the C++ step splits the wave
+    e.l("v_readfirstlane_b32 s68, %s", Y0);
+    e.l("v_readfirstlane_b32 s69, %s", Y1);
+    e.l("s_nop 1");
+    e.l("v_cmp_ne_u32_e64 %s, s68, %s", T2, Y0);
+    e.l("v_cmp_ne_u32_e32 vcc, s69, %s", Y1);
+    e.l("s_or_b64 %s, %s, vcc", T2, T2);
+    e.l("s_and_b64 %s, %s, exec", T2, T2);
+    if (sx & 1) {
+      e.l("s_cbranch_scc1 Lts%s", K.c_str());
+      Em x(t);
+      x.l("Lts%s:", K.c_str());
+      x.l("v_mov_b32 %s, %s", VPC, Y0);
+      x.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, Y1);
+      x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+      flush(x);
+      long_jump(x, "Lsched", "Ltq" + K);
+      extra += x.o;
+    } else {
+      const std::string lab_split = "Lx" + K + "_" + std::to_string(e.stubs.size());
+      e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone});
+      e.l("s_cbranch_scc1 %s", lab_split.c_str());
+    }
+    e.l("s_lshl_b32 s62, s68, 5");
+    e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+    e.l("s_add_u32 s65, s65, s69");
+    taken_checks();
+    go(~0u, false);
+  }
+  void tail_branch() {
+    const uint32_t bcnt = (last.w0 >> 16) & 0xFFu;
+    const int32_t tcnt = int32_t(int16_t(last.w2 >> 16));
+    const uint32_t taken_cnt = uint32_t(int32_t(r.cnt) + tcnt);   // (cnt + tcnt >= 0)
+    const std::string nt = "Lnt" + K;
+    if (lop != OP_JMP) {
+      if (cmp_any) {   // VCC = the lanes whose any_true is 1
+        if (lop == OP_BR_UNLESS) e.l("s_not_b64 vcc, vcc");
+      } else {
+        if (fuse_cell != ~0u) {   // (the fused any_true's OR is in R0)
+          e.alias_cell = int64_t(fuse_cell);
+          e.alias_reg = 114;
+        }
+        branch_cond(e, last);
+        e.alias_cell = -1;
       }
-    } else if (lop == OP_BR_TABLE) {
-      emit_br_table(e, last);
-      // every lane to the same entry: jump there (count + that entry's correction);
-      // else (SIMT) each lane records its target and count and the scheduler picks, or
-      // (no SIMT) the C++ step splits the wave
-      e.l("v_readfirstlane_b32 s68, %s", Y0);
-      e.l("v_readfirstlane_b32 s69, %s", Y1);
-      e.l("s_nop 1");
-      e.l("v_cmp_ne_u32_e64 %s, s68, %s", T2, Y0);
-      e.l("v_cmp_ne_u32_e32 vcc, s69, %s", Y1);
-      e.l("s_or_b64 %s, %s, vcc", T2, T2);
-      e.l("s_and_b64 %s, %s, exec", T2, T2);
+      e.l("s_and_b64 %s, vcc, exec", T2);
+      e.l("s_cbranch_scc0 %s", nt.c_str());    // no lane takes it
+      e.l("s_cmp_eq_u64 %s, exec", T2);
       if (sx & 1) {
-        e.l("s_cbranch_scc1 Lts%s", K.c_str());
-        Em x;
-        x.l("Lts%s:", K.c_str());
-        x.l("v_mov_b32 %s, %s", VPC, Y0);
-        x.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, Y1);
+        // lanes disagree: each records where it goes on (vcc: taken) and its count,
+        // and the scheduler picks who goes first
+        e.l("s_cbranch_scc0 Lbs%s", K.c_str());
+        Em x(t);
+        x.l("Lbs%s:", K.c_str());
+        {   // (inline constants where they fit: VOP3 selects take -16..64)
+          auto inl = [](int64_t v) { return v >= -16 && v <= 64; };
+          std::string f = std::to_string(fall), t = std::to_string(tgt);
+          if (!inl(fall)) { x.l("v_mov_b32 %s, 0x%x", X0, fall); f = X0; }
+          if (!inl(tgt)) { x.l("v_mov_b32 %s, 0x%x", X1, tgt); t = X1; }
+          x.l("v_cndmask_b32_e64 %s, %s, %s, vcc", VPC, f.c_str(), t.c_str());
+          if (inl(tcnt)) {   // a taken branch's correction
+            x.l("v_cndmask_b32_e64 %s, 0, %d, vcc", X0, int32_t(tcnt));
+          } else {
+            x.l("v_mov_b32 %s, 0x%x", X1, uint32_t(tcnt));
+            x.l("v_cndmask_b32_e32 %s, 0, %s, vcc", X0, X1);
+          }
+          x.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, X0);
+        }
         x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
         flush(x);
-        long_jump(x, "Lsched", "Ltq" + K);
+        if (fall != tgt && !hybrid && !depth_pick) {   // (hybrid: every split goes to Lsched, hence the trips)
+          // No waiting lane at or below the nearer destination `lo`: the lanes going
+          // there are the next group, those going to `hi` wait, and the lowest waiting
+          // pc becomes min(LOW, hi) -- a pick without the wave reductions of Lsched
+          const uint32_t lo = std::min(fall, tgt), hi = std::max(fall, tgt);
+          x.l("s_cmp_le_u32 s95, 0x%x", lo * 32u);
+          x.l("s_cbranch_scc0 Lbf%s", K.c_str());
+          long_jump(x, "Lsched", "Lbq" + K);
+          x.l("Lbf%s:", K.c_str());
+          x.l("s_sub_u32 s64, s64, 16");
+          x.l("s_cselect_b32 s64, 0, s64");
+          x.l("s_cmp_eq_u32 s95, -1");                  // converged until now: D banks
+          x.l("s_cbranch_scc0 Lbm%s", K.c_str());
+          x.l("s_add_u32 s70, s70, 0x%x", 2u * TC_BANK_BYTES);
+          x.l("s_addc_u32 s71, s71, 0");
+          x.l("s_add_u32 s72, s70, 0x%x", TC_BANK_BYTES);
+          x.l("s_addc_u32 s73, s71, 0");
+          x.l("Lbm%s:", K.c_str());
+          x.l("s_min_u32 s95, s95, 0x%x", hi * 32u);
+          x.l("s_mov_b32 s63, s95");
+          x.l(lo == tgt ? "s_and_b64 s[74:75], vcc, exec" : "s_andn2_b64 s[74:75], exec, vcc");
+          x.l("s_mov_b32 s62, 0x%x", lo * 32u);
+          x.l("s_waitcnt lgkmcnt(0)");
+          x.l("s_load_dwordx8 s[76:83], s[60:61], s62");
+          x.l("s_load_dwordx8 s[84:91], s[60:61], s62 offset:0x20");
+          long_jump(x, "Lsc_disp", "Lbt" + K);   // (clobbers s[68:69])
+        } else {
+          long_jump(x, "Lsched", "Lbq" + K);
+        }
         extra += x.o;
       } else {
         const std::string lab_split = "Lx" + K + "_" + std::to_string(e.stubs.size());
         e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone});
-        e.l("s_cbranch_scc1 %s", lab_split.c_str());
+        e.l("s_cbranch_scc0 %s", lab_split.c_str());   // lanes disagree: the C++ step splits
       }
-      e.l("s_lshl_b32 s62, s68, 5");
-      e.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-      e.l("s_add_u32 s65, s65, s69");
-      taken_checks();
-      go(~0u, false);
-    } else if (is_branch_op(lop)) {
-      const uint32_t bcnt = (last.w0 >> 16) & 0xFFu;
-      const int32_t tcnt = int32_t(int16_t(last.w2 >> 16));
-      const uint32_t taken_cnt = uint32_t(int32_t(r.cnt) + tcnt);   // (cnt + tcnt >= 0)
-      const std::string nt = "Lnt" + K;
-      if (lop != OP_JMP) {
-        if (cmp_any) {   // VCC = the lanes whose any_true is 1
-          if (lop == OP_BR_UNLESS) e.l("s_not_b64 vcc, vcc");
-        } else {
-          if (fuse_cell != ~0u) {   // (the fused any_true's OR is in R0)
-            e.alias_cell = int64_t(fuse_cell);
-            e.alias_reg = 114;
-          }
-          branch_cond(e, last);
-          e.alias_cell = -1;
-        }
-        e.l("s_and_b64 %s, vcc, exec", T2);
-        e.l("s_cbranch_scc0 %s", nt.c_str());    // no lane takes it
-        e.l("s_cmp_eq_u64 %s, exec", T2);
-        if (sx & 1) {
-          // lanes disagree: each records where it goes on (vcc: taken) and its count,
-          // and the scheduler picks who goes first
-          e.l("s_cbranch_scc0 Lbs%s", K.c_str());
-          Em x;
-          x.l("Lbs%s:", K.c_str());
-          {   // (inline constants where they fit: VOP3 selects take -16..64)
-            auto inl = [](int64_t v) { return v >= -16 && v <= 64; };
-            std::string f = std::to_string(fall), t = std::to_string(tgt);
-            if (!inl(fall)) { x.l("v_mov_b32 %s, 0x%x", X0, fall); f = X0; }
-            if (!inl(tgt)) { x.l("v_mov_b32 %s, 0x%x", X1, tgt); t = X1; }
-            x.l("v_cndmask_b32_e64 %s, %s, %s, vcc", VPC, f.c_str(), t.c_str());
-            if (inl(tcnt)) {   // a taken branch's correction
-              x.l("v_cndmask_b32_e64 %s, 0, %d, vcc", X0, int32_t(tcnt));
-            } else {
-              x.l("v_mov_b32 %s, 0x%x", X1, uint32_t(tcnt));
-              x.l("v_cndmask_b32_e32 %s, 0, %s, vcc", X0, X1);
-            }
-            x.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, X0);
-          }
-          x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
-          flush(x);
-          if (fall != tgt && !hybrid && !depth_pick) {   // (hybrid: every split goes to Lsched, hence the trips)
-            // No waiting lane at or below the nearer destination `lo`: the lanes going
-            // there are the next group, those going to `hi` wait, and the lowest waiting
-            // pc becomes min(LOW, hi) -- a pick without the wave reductions of Lsched
-            const uint32_t lo = std::min(fall, tgt), hi = std::max(fall, tgt);
-            x.l("s_cmp_le_u32 s95, 0x%x", lo * 32u);
-            x.l("s_cbranch_scc0 Lbf%s", K.c_str());
-            long_jump(x, "Lsched", "Lbq" + K);
-            x.l("Lbf%s:", K.c_str());
-            x.l("s_sub_u32 s64, s64, 16");
-            x.l("s_cselect_b32 s64, 0, s64");
-            x.l("s_cmp_eq_u32 s95, -1");                  // converged until now: D banks
-            x.l("s_cbranch_scc0 Lbm%s", K.c_str());
-            x.l("s_add_u32 s70, s70, 0x%x", 2u * TC_BANK_BYTES);
-            x.l("s_addc_u32 s71, s71, 0");
-            x.l("s_add_u32 s72, s70, 0x%x", TC_BANK_BYTES);
-            x.l("s_addc_u32 s73, s71, 0");
-            x.l("Lbm%s:", K.c_str());
-            x.l("s_min_u32 s95, s95, 0x%x", hi * 32u);
-            x.l("s_mov_b32 s63, s95");
-            x.l(lo == tgt ? "s_and_b64 s[74:75], vcc, exec" : "s_andn2_b64 s[74:75], exec, vcc");
-            x.l("s_mov_b32 s62, 0x%x", lo * 32u);
-            x.l("s_waitcnt lgkmcnt(0)");
-            x.l("s_load_dwordx8 s[76:83], s[60:61], s62");
-            x.l("s_load_dwordx8 s[84:91], s[60:61], s62 offset:0x20");
-            long_jump(x, "Lsc_disp", "Lbt" + K);   // (clobbers s[68:69])
-          } else {
-            long_jump(x, "Lsched", "Lbq" + K);
-          }
-          extra += x.o;
-        } else {
-          const std::string lab_split = "Lx" + K + "_" + std::to_string(e.stubs.size());
-          e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone});
-          e.l("s_cbranch_scc0 %s", lab_split.c_str());   // lanes disagree: the C++ step splits
-        }
-      }
-      e.gas_add(uint64_t(int64_t(c_fall) + c_adj));
-      e.l("s_add_u32 s65, s65, 0x%x", taken_cnt);
-      fast_to(tgt, true, false);
-      e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
-      taken_checks();
-      go(tgt, false);
-      if (lop != OP_JMP) {
-        e.l("%s:", nt.c_str());
-        (void)bcnt;
-        fallthrough(r.cnt);
-      }
-    } else {
+    }
+    e.gas_add(uint64_t(int64_t(c_fall) + c_adj));
+    e.l("s_add_u32 s65, s65, 0x%x", taken_cnt);
+    fast_to(tgt, true, false);
+    e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
+    taken_checks();
+    go(tgt, false);
+    if (lop != OP_JMP) {
+      e.l("%s:", nt.c_str());
+      (void)bcnt;
       fallthrough(r.cnt);
     }
+  }
+
+  // the exit to the scheduler, the out-of-line code and the leave stubs
+  void finish() {
     e.l("Lxs%s:", K.c_str());
     if (sx & 4) {   // reached a waiting lane or the count limit: merge / reschedule
       long_jump(e, "Lmerge", "Lmq" + K);
@@ -4795,9 +4676,72 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
       e.l("s_add_u32 s65, s65, 0x%x", s.done);
       e.l("s_setpc_b64 s[70:71]");
     }
-    body += e.o;
   }
-  if (hybrid) body += trip_source(P, runs, glog, true);
+
+  bool compile() {
+    entry();
+    if (!body()) return false;
+    if (pl.inl_f[k] >= 0) {
+      if (!tail_inlined()) return false;
+    } else if (lop == OP_TAIL_CALL) {
+      tail_tail_call();
+    } else if (lop == OP_CALL) {
+      tail_call();
+    } else if (lop == OP_RET) {
+      tail_ret();
+    } else if (lop == OP_BR_TABLE) {
+      tail_br_table();
+    } else if (is_branch_op(lop)) {
+      tail_branch();
+    } else {
+      fallthrough(r.cnt);
+    }
+    finish();
+    return true;
+  }
+};
+
+}  // namespace
+
+std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32_t glog,
+                       const JitCost *cost, bool simt, bool trip, const std::vector<uint32_t> *xinfo,
+                       uint32_t xlog, uint32_t mem_pages) {
+  if (cost) simt = false;
+  // (extra memories: their accesses compile only against the context's word offsets)
+  if (!P.xmems.empty() && (!xinfo || xinfo->size() < 2 * P.xmems.size())) return "";
+  const JitKnobs kn = read_knobs();
+  const JitTarget t{P, glog, cost, xinfo, xlog, mem_pages};
+  const RunIndex ix(P, runs);
+  // trip mode beside SIMT scheduling (hybrid, the default) or alone (WB_HYBRID=0)
+  const bool trips = trip && simt && runs.size() <= kTripMaxRuns;
+  const bool hybrid = trips && kn.hybrid;
+  if (trips && !hybrid) return trip_source(t, kn, ix, runs, false);
+  // NaN fixes only where the payload can be observed (WB_NANOBS=0: everywhere)
+  const std::vector<uint8_t> nob = kn.nanobs ? nan_observable(P, kn) : std::vector<uint8_t>();
+  const SimtPlan pl = plan_simt(t, kn, ix, runs);
+  // which divergence events stay in the core (debug aid): 1 split branches, 2 split
+  // returns, 4 reaching a waiting lane / the count limit (else the core leaves as without
+  // SIMT)
+  const unsigned sx = simt ? kn.simt_x : 0u;
+  // One asm statement holds every run (behind a jump) and a table of their offsets from
+  // the table itself; the kernel reads the table and writes the absolute addresses.
+  std::string body;
+  body += "s_getpc_b64 s[6:7]\nLpt:\ns_add_u32 s6, s6, Ltab - Lpt\ns_addc_u32 s7, s7, 0\n"
+          "s_mov_b32 %0, s6\ns_mov_b32 %1, s7\n"
+          "s_getpc_b64 s[8:9]\nLpe:\ns_add_u32 s8, s8, Lend - Lpe\ns_addc_u32 s9, s9, 0\n"
+          "s_setpc_b64 s[8:9]\n";
+  // Recursive modules pick groups by call-stack height first (sched_block); their split
+  // branches go through that pick too (the pc-only shortcut, Lbf, would undo it).
+  // WB_DEPTH=0: pc-only picks everywhere (A/B aid)
+  const bool depth_pick = simt && kn.depth && recursive(P);
+  if (simt) body += simt_sched(t, hybrid, depth_pick);
+  const SimtCtx ctx{t, kn, ix, runs, pl, nob, sx, hybrid, depth_pick};
+  for (const auto &job : pl.jobs) {
+    RunCompile rc(ctx, job.first, job.second);
+    if (!rc.compile()) return "";   // jit_runs only picks compilable instructions
+    body += rc.e.o;
+  }
+  if (hybrid) body += trip_source(t, kn, ix, runs, true);
   body = resolve_jumps(body);
   body += ".p2align 3\nLtab:\n";
   for (size_t k = 0; k < runs.size(); k++) body += ".quad Lb" + std::to_string(k) + " - Ltab\n";
@@ -4864,178 +4808,4 @@ bool trips_pay(const Program &P) {
   return false;
 }
 
-std::string jit_compile(const std::string &src, std::vector<char> *code, const std::string &arch) {
-  hiprtcProgram prog;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "wbjit.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-    return "hiprtcCreateProgram failed";
-  const std::string target = "--offload-arch=" + arch;
-  const char *opts[] = {target.c_str(), "-O1"};
-  if (hiprtcCompileProgram(prog, 2, opts) != HIPRTC_SUCCESS) {
-    size_t n = 0;
-    hiprtcGetProgramLogSize(prog, &n);
-    std::string log(n + 1, '\0');
-    hiprtcGetProgramLog(prog, log.data());
-    hiprtcDestroyProgram(&prog);
-    return "compiled-run assembly failed: " + log.substr(0, 2000);
-  }
-  size_t sz = 0;
-  hiprtcGetCodeSize(prog, &sz);
-  code->assign(sz, 0);
-  hiprtcGetCode(prog, code->data());
-  hiprtcDestroyProgram(&prog);
-  return "";
-}
-
-std::string jit_load(const std::string &src, size_t nruns, int device, std::vector<uint64_t> *addr) {
-  // one code object per (HIP context, device, source) while that context lives: contexts
-  // of the same module share it (a new primary context after hipDeviceReset gets its own)
-  static std::mutex mu;
-  static std::map<std::tuple<uintptr_t, int, std::string>, std::vector<uint64_t>> cache;
-  std::lock_guard<std::mutex> lock(mu);
-  hipCtx_t hctx = nullptr;
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wdeprecated-declarations"
-  (void)hipCtxGetCurrent(&hctx);
-#pragma clang diagnostic pop
-  const auto key = std::make_tuple(uintptr_t(hctx), device, src);
-  auto it = cache.find(key);
-  if (it != cache.end()) { *addr = it->second; return ""; }
-  // the device's own target (gfx950 on MI355X), not a hard-coded one
-  std::string arch = "gfx950";
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.gcnArchName[0]) {
-    arch = prop.gcnArchName;
-    const size_t colon = arch.find(':');   // (feature suffixes such as :sramecc+:xnack-)
-    if (colon != std::string::npos) arch.resize(colon);
-  }
-  std::vector<char> code;
-  std::string err = jit_compile(src, &code, arch);
-  if (!err.empty()) return err;
-  hipModule_t mod;
-  if (hipModuleLoadData(&mod, code.data()) != hipSuccess) return "hipModuleLoadData failed";
-  hipFunction_t fn;
-  if (hipModuleGetFunction(&fn, mod, "wbjit_addrs") != hipSuccess) return "hipModuleGetFunction failed";
-  uint64_t *dout = nullptr;
-  if (hipMalloc(&dout, std::max<size_t>(1, nruns) * 8) != hipSuccess) return "hipMalloc failed";
-  unsigned nr = unsigned(nruns);
-  void *args[] = {&dout, &nr};
-  std::vector<uint64_t> a(nruns, 0);
-  // (a private stream: BatchCreate must not wait for other contexts' kernels)
-  hipStream_t qs = nullptr;
-  const bool ok = hipStreamCreateWithFlags(&qs, hipStreamNonBlocking) == hipSuccess &&
-                  hipModuleLaunchKernel(fn, 1, 1, 1, 64, 1, 1, 0, qs, args, nullptr) == hipSuccess &&
-                  hipMemcpyAsync(a.data(), dout, nruns * 8, hipMemcpyDeviceToHost, qs) == hipSuccess &&
-                  hipStreamSynchronize(qs) == hipSuccess;
-  if (qs) (void)hipStreamDestroy(qs);
-  (void)hipFree(dout);
-  if (!ok) return "compiled-run address query failed";
-  for (uint64_t x : a)
-    if (x == 0 || (x & 63)) return "compiled-run address query returned a bad address";
-  cache[key] = a;   // the module stays loaded: its code is jumped to
-  *addr = a;
-  return "";
-}
-
-void jit_patch(std::vector<TInstr> &tc, const std::vector<JitRun> &runs, const std::vector<uint64_t> &addr) {
-  for (size_t k = 0; k < runs.size(); k++) {
-    uint32_t *w = tc[runs[k].pc].w;
-    w[0] = TC_SLOT_JIT * TC_SLOT_BYTES;
-    w[1] = uint32_t(addr[k]);
-    w[2] = uint32_t(addr[k] >> 32);
-    w[3] = w[4] = w[6] = w[7] = 0;
-    w[5] = (runs[k].len - 1) * 32u;
-  }
-}
-
 }  // namespace wb
-
-// TEST hook (tests/test_jit.py, CPU): lower a module, pick its runs and assemble them for
-// gfx950 without a device. Returns the number of runs, or -1 with the error in err.
-extern "C" __attribute__((visibility("default"))) int wb_jit_check(const uint8_t *wasm, uint32_t len,
-                                                                   uint32_t glog, uint32_t *instrs,
-                                                                   char *err, uint32_t errlen) {
-  wb::Program P;
-  uint8_t ec = 0;
-  std::string e = wb::load_program(wasm, len, P, &ec, false, nullptr, true, true);
-  std::vector<wb::JitRun> runs;
-  if (e.empty() && P.total_cells() > TC_VF_CELLS) e = "frame too large for V frames";
-  // extra memories laid out at their minimum sizes (batch_api.cpp reserves more for grown ones)
-  std::vector<uint32_t> xinfo;
-  uint64_t words = 0;
-  for (const auto &xm : P.xmems) {
-    xinfo.push_back(uint32_t(words));
-    xinfo.push_back(xm.min);
-    words += uint64_t(xm.min) << 14;
-  }
-  if (e.empty()) {
-    std::vector<DInstr> code = P.code;
-    code.push_back(DInstr{0, 0, 0, 0});
-    const std::vector<TInstr> tc = wb::build_threaded(P, code, true);
-    runs = wb::jit_runs(P, tc);
-    // debug listing: every DBC instruction (op, fields) with the SIMT run it belongs to
-    if (const char *lst = getenv("WB_JIT_LIST"))
-      if (FILE *f = fopen(lst, "w")) {
-        static const char *const names[] = {
-#define WB_NAME(x) #x,
-            DBC_OPS(WB_NAME)
-#undef WB_NAME
-        };
-        const std::vector<wb::JitRun> sr = wb::jit_runs(P, tc, true);
-        std::vector<int> at(P.code.size(), -1);
-        for (size_t k = 0; k < sr.size(); k++)
-          for (uint32_t i = 0; i < sr[k].len; i++) at[sr[k].pc + i] = int(k);
-        for (size_t pc = 0; pc < P.code.size(); pc++) {
-          const DInstr &I = P.code[pc];
-          const uint16_t op = uint16_t(I.w0 & 0x7FFFu);
-          fprintf(f, "%4zu %s%-4s %-22s a=%u b=%u c=%u d=%d imm=0x%x cnt=%u\n", pc,
-                  at[pc] >= 0 && sr[at[pc]].pc == pc ? "R" : " ",
-                  at[pc] >= 0 ? std::to_string(at[pc]).c_str() : "-",
-                  op < OP_DBC_NUM_OPS ? names[op] : "?", I.w1 & 0xFFFFu, I.w1 >> 16, I.w2 & 0xFFFFu,
-                  int(int16_t(I.w2 >> 16)), I.w3, (I.w0 >> 16) & 0xFFu);
-        }
-        fclose(f);
-      }
-    if (instrs) {
-      *instrs = 0;
-      for (const auto &r : runs) *instrs += r.len;
-    }
-    // every flavour: plain runs, SIMT scheduling (KParams::simt, its own run choice) and
-    // trip mode (its own run choice too)
-    for (int simt = 0; simt < 3 && e.empty(); simt++) {
-      if (simt) runs = wb::jit_runs(P, tc, true, simt == 2);
-      if (runs.empty()) continue;
-      std::vector<char> obj;
-      // (a memory below kMadPages unless WB_JIT_CHECK_PAGES says otherwise: the 32-bit
-      // granule addresses of trip stages assembled too)
-      const char *cp = getenv("WB_JIT_CHECK_PAGES");
-      const std::string src = wb::jit_source(P, runs, glog, nullptr, simt != 0, simt == 2, &xinfo,
-                                             P.divergent_xmem ? 5u : 0u, cp ? uint32_t(atoi(cp)) : wb::kMadPages);
-      if (const char *dump = getenv(simt == 2 ? "WB_JIT_DUMP_TRIP" : simt ? "WB_JIT_DUMP_SIMT" : "WB_JIT_DUMP"))
-        if (FILE *f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
-      e = src.empty() ? "no source" : wb::jit_compile(src, &obj);
-    }
-  }
-  if (!e.empty()) {
-    if (err && errlen) snprintf(err, errlen, "%s", e.c_str());
-    return -1;
-  }
-  return int(runs.size());
-}
-
-// TEST hook (tests/test_jit.py, CPU): whether a SIMT context of this module runs trip mode
-// (Program::divergent_mem or wb::trips_pay; WB_TRIP unset). 1 / 0, or -1 when it fails to load.
-extern "C" __attribute__((visibility("default"))) int wb_trip_choice(const uint8_t *wasm, uint32_t len) {
-  wb::Program P;
-  uint8_t ec = 0;
-  if (!wb::load_program(wasm, len, P, &ec).empty()) return -1;
-  return P.divergent_mem || P.divergent_xmem || wb::trips_pay(P) ? 1 : 0;
-}
-
-// TEST hook (tests/test_depth_pick.py, CPU): whether the module counts as recursive for the
-// depth-keyed SIMT pick (wb::recursive). 1 / 0, or -1 when it fails to load.
-extern "C" __attribute__((visibility("default"))) int wb_recursive(const uint8_t *wasm, uint32_t len) {
-  wb::Program P;
-  uint8_t ec = 0;
-  if (!wb::load_program(wasm, len, P, &ec).empty()) return -1;
-  return wb::recursive(P) ? 1 : 0;
-}
