@@ -496,6 +496,50 @@ WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchGetMemory(WasmEdge_BatchContext
 WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchSetMemory(WasmEdge_BatchContext *Cxt,
                                                            uint32_t Inst, uint32_t Off,
                                                            const uint8_t *Src, uint32_t Len);
+/* Bulk transfer: linear memory 0 of EVERY instance in one call -- the batched form of
+ * WasmEdge_MemoryInstanceSetData / GetData (wasmedge.h:2552-2569), which the reference has
+ * once per VM. Instance i moves len_i = Lens ? Lens[i] : Len bytes between row i of a
+ * [NumInstances][Stride] byte buffer (byte i * Stride onward) and its memory, starting at
+ * Offset + (Offsets ? Offsets[i] : 0), computed in 64 bits (a guest allocator returns a
+ * different pointer per instance: Offsets would come from a previous run's results).
+ * Offsets, Lens and PerInstance are host arrays [NumInstances], each may be NULL.
+ *
+ * Per instance, the reference's bound check (include/runtime/instance/memory.h:74-78): a
+ * range that ends past the instance's current size gives PerInstance[i] = MemoryOutOfBounds
+ * (0x88) and moves nothing of that instance -- its memory and its row of Dst stay as they
+ * are; otherwise PerInstance[i] = 0 (also for len_i = 0 with the start within the size).
+ * A read leaves the bytes of a row past len_i untouched. The call-level result is 0 even
+ * when instances are out of bounds. Call-level failures, nothing moved: NULL context, NULL
+ * Src / Dst with Len != 0, Stride < Len or some Lens[i] > Len give WrongVMWorkflow (0x04); a
+ * module without a memory gives 0x88, as WasmEdge_BatchGetMemory does for any range.
+ *
+ * The call returns when the transfer is complete; it orders after a BatchReset that did
+ * not wait (KernelSeconds NULL). Writes persist until BatchReset, like
+ * WasmEdge_BatchSetMemory. Not to be called from inside a host function.
+ *
+ * The Device variants take Src / Dst as a device pointer to a buffer on the context's
+ * device (for a torch tensor, its data_ptr): the rows never cross the host. The CALLER makes
+ * sure that whatever produced the buffer has finished before the call (synchronise the
+ * stream that wrote it); the library synchronises its own stream before it returns. On a
+ * multi-device context one device buffer cannot serve several devices: they fail with
+ * RuntimeError (0x02) and a WasmEdge_BatchGetLastError message; the host variants slice
+ * Offsets, Lens and the rows by the placement and gather PerInstance in instance order. */
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchWriteMemories(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets, uint32_t Offset,
+                            const uint32_t *Lens, uint32_t Len, const uint8_t *Src,
+                            uint64_t Stride, uint8_t *PerInstance);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchReadMemories(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets, uint32_t Offset,
+                           const uint32_t *Lens, uint32_t Len, uint8_t *Dst, uint64_t Stride,
+                           uint8_t *PerInstance);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchWriteMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets,
+                                  uint32_t Offset, const uint32_t *Lens, uint32_t Len,
+                                  const uint8_t *Src, uint64_t Stride, uint8_t *PerInstance);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets,
+                                 uint32_t Offset, const uint32_t *Lens, uint32_t Len, uint8_t *Dst,
+                                 uint64_t Stride, uint8_t *PerInstance);
 /* Exported tables and globals of one instance, by export name (the batched form of
  * WasmEdge_StoreFindTable/FindGlobal + WasmEdge_TableInstanceGetData/SetData/GetSize,
  * lib/api/wasmedge.cpp:2099-2139, and WasmEdge_GlobalInstanceGetValue/SetValue,

@@ -152,6 +152,10 @@ def lib():
             ("WasmEdge_BatchExecuteCalls", [vp, ctypes.POINTER(_String), u32, vp, vp, u32, vp,
                                             vp, u32, vp, vp, vp]),
             ("WasmEdge_BatchGetReturnLens", [vp, vp]),
+            ("WasmEdge_BatchWriteMemories", [vp, vp, u32, vp, u32, vp, u64, vp]),
+            ("WasmEdge_BatchReadMemories", [vp, vp, u32, vp, u32, vp, u64, vp]),
+            ("WasmEdge_BatchWriteMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
+            ("WasmEdge_BatchReadMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
         ]:
             f = getattr(L, name)
             f.restype = _Result
@@ -464,6 +468,89 @@ class BatchContext:
 
     def set_memory(self, inst, off, data):
         self._check(lib().WasmEdge_BatchSetMemory(self._h, inst, off, bytes(data), len(data)))
+
+    # bulk transfer: every instance's linear memory in one call (WasmEdge_BatchWriteMemories /
+    # ReadMemories and their Device variants). Instance i moves lens[i] (default: the row
+    # length) bytes between row i and its memory at offset + offsets[i]; the returned status is
+    # 0 or 0x88 per instance (out of bounds: that instance moved nothing).
+    def _spans(self, offsets, lens):
+        off = ln = None
+        if offsets is not None:
+            off = np.ascontiguousarray(offsets, np.uint32)
+            if off.shape != (self.n,):
+                raise ValueError("offsets must have %d entries" % self.n)
+        if lens is not None:
+            ln = np.ascontiguousarray(lens, np.uint32)
+            if ln.shape != (self.n,):
+                raise ValueError("lens must have %d entries" % self.n)
+        return off, ln, (off.ctypes.data if off is not None else None,
+                         ln.ctypes.data if ln is not None else None)
+
+    def write_memories(self, data, offset=0, offsets=None, lens=None, length=None):
+        """data: a uint8 array [n, stride], or a list of n bytes objects (padded to the
+        longest; lens defaults to their lengths). length: the bytes of a row that count
+        (default: the stride). Returns the status array."""
+        if not isinstance(data, np.ndarray):
+            items = [bytes(d) for d in data]
+            if lens is None:
+                lens = [len(d) for d in items]
+            arr = np.zeros((len(items), max([len(d) for d in items] + [0])), np.uint8)
+            for i, d in enumerate(items):
+                arr[i, :len(d)] = np.frombuffer(d, np.uint8)
+            data = arr
+        data = np.ascontiguousarray(data, np.uint8)
+        if data.ndim != 2 or data.shape[0] != self.n:
+            raise ValueError("data must be [%d instances][stride], got shape %s" % (self.n, data.shape))
+        off, ln, (po, pl) = self._spans(offsets, lens)
+        status = np.zeros(self.n, np.uint8)
+        length = data.shape[1] if length is None else length
+        self._check(lib().WasmEdge_BatchWriteMemories(self._h, po, offset, pl, length,
+                                                      data.ctypes.data if data.size else None,
+                                                      data.shape[1], status.ctypes.data))
+        return status
+
+    def read_memories(self, length, offset=0, offsets=None, lens=None, out=None):
+        """(uint8[n, length], status): row i holds instance i's bytes (zeros where it read
+        nothing: past lens[i], or the whole row when its status is 0x88). out: a contiguous
+        uint8 array [n, stride >= length] to read into instead; what an instance does not
+        fill stays as it is."""
+        if out is None:
+            out = np.zeros((self.n, length), np.uint8)
+        if out.dtype != np.uint8 or out.ndim != 2 or out.shape[0] != self.n or not out.flags.c_contiguous:
+            raise ValueError("out must be a contiguous uint8 array [%d instances][stride]" % self.n)
+        off, ln, (po, pl) = self._spans(offsets, lens)
+        status = np.zeros(self.n, np.uint8)
+        self._check(lib().WasmEdge_BatchReadMemories(self._h, po, offset, pl, length,
+                                                     out.ctypes.data if out.size else None, out.shape[1],
+                                                     status.ctypes.data))
+        return out, status
+
+    def _tensor_io(self, fn, t, offset, offsets, lens):
+        import torch
+        if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] != self.n or not t.is_contiguous() \
+                or not t.is_cuda:
+            raise ValueError("a contiguous torch.uint8 tensor [%d, stride] on the device is needed" % self.n)
+        off, ln, (po, pl) = self._spans(offsets, lens)
+        status = np.zeros(self.n, np.uint8)
+        # the library does not know the stream that produced (or will consume) the tensor
+        with torch.cuda.device(t.device):
+            torch.cuda.current_stream().synchronize()
+        self._check(fn(self._h, po, offset, pl, t.shape[1], t.data_ptr() if t.numel() else None,
+                       t.shape[1], status.ctypes.data))
+        return status
+
+    def write_memories_tensor(self, t, offset=0, offsets=None, lens=None):
+        """write_memories from a contiguous torch.uint8 tensor [n, stride] on the context's
+        device: the rows never cross the host. Returns the status array. A torch build that
+        brings a HIP runtime of its own has to initialise the device (torch.cuda.init())
+        before the process creates its first BatchContext: started second, that runtime
+        finds no GPU."""
+        return self._tensor_io(lib().WasmEdge_BatchWriteMemoriesDevice, t, offset, offsets, lens)
+
+    def read_memories_tensor(self, t, offset=0, offsets=None, lens=None):
+        """read_memories into such a tensor (bytes an instance does not fill stay as they
+        are). Returns the status array."""
+        return self._tensor_io(lib().WasmEdge_BatchReadMemoriesDevice, t, offset, offsets, lens)
 
     # exported tables / globals of one instance (WasmEdge_TableInstance*/GlobalInstance*);
     # inst=None writes every instance

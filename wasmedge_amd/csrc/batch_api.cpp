@@ -1178,6 +1178,46 @@ WasmEdge_Result WasmEdge_BatchSetMemory(WasmEdge_BatchContext *C, uint32_t Inst,
   return R(mem_rw(C, Inst, Off, Len, nullptr, Src));
 }
 
+// The four bulk transfers: the call-level checks (nothing moved when one fails), then the
+// shards (multi.cpp) or the device (hostcall.cpp mem_io).
+static WasmEdge_Result bulk_memories(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offset,
+                                     const uint32_t *Lens, uint32_t Len, uint8_t *Buf, uint64_t Stride,
+                                     uint8_t *PerInstance, bool write, bool device) {
+  if (!C || (!Buf && Len) || Stride < Len) return R(kWrongVMWorkflow);
+  for (uint32_t i = 0; Lens && i < C->n; i++)
+    if (Lens[i] > Len) return R(kWrongVMWorkflow);
+  const WasmEdge_BatchContext *one = C->shards.empty() ? C : wbm::first(C);
+  if (one && !one->prog.has_mem) return R(kMemoryOutOfBounds);
+  if (C->shards.empty()) return R(mem_io(C, Offsets, Offset, Lens, Len, Buf, Stride, PerInstance, write, device));
+  if (device)
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use the host variant"));
+  return wbm::mem_io(C, Offsets, Offset, Lens, Len, Buf, Stride, PerInstance, write);
+}
+
+WasmEdge_Result WasmEdge_BatchWriteMemories(WasmEdge_BatchContext *C, const uint32_t *Offsets,
+                                            uint32_t Offset, const uint32_t *Lens, uint32_t Len,
+                                            const uint8_t *Src, uint64_t Stride, uint8_t *PerInstance) {
+  return bulk_memories(C, Offsets, Offset, Lens, Len, const_cast<uint8_t *>(Src), Stride, PerInstance, true, false);
+}
+
+WasmEdge_Result WasmEdge_BatchReadMemories(WasmEdge_BatchContext *C, const uint32_t *Offsets,
+                                           uint32_t Offset, const uint32_t *Lens, uint32_t Len,
+                                           uint8_t *Dst, uint64_t Stride, uint8_t *PerInstance) {
+  return bulk_memories(C, Offsets, Offset, Lens, Len, Dst, Stride, PerInstance, false, false);
+}
+
+WasmEdge_Result WasmEdge_BatchWriteMemoriesDevice(WasmEdge_BatchContext *C, const uint32_t *Offsets,
+                                                  uint32_t Offset, const uint32_t *Lens, uint32_t Len,
+                                                  const uint8_t *Src, uint64_t Stride, uint8_t *PerInstance) {
+  return bulk_memories(C, Offsets, Offset, Lens, Len, const_cast<uint8_t *>(Src), Stride, PerInstance, true, true);
+}
+
+WasmEdge_Result WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *C, const uint32_t *Offsets,
+                                                 uint32_t Offset, const uint32_t *Lens, uint32_t Len,
+                                                 uint8_t *Dst, uint64_t Stride, uint8_t *PerInstance) {
+  return bulk_memories(C, Offsets, Offset, Lens, Len, Dst, Stride, PerInstance, false, true);
+}
+
 // ---- exported tables and globals (WasmEdge_TableInstance{Get,Set}Data / GetSize,
 // WasmEdge_GlobalInstance{Get,Set}Value, lib/api/wasmedge.cpp:2099-2139, 2273-2295),
 // per instance; Inst = WASMEDGE_BATCH_ALL_INSTANCES writes every instance

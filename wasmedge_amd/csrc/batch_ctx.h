@@ -16,6 +16,7 @@
 #include "frontend.h"
 #include "tc.h"
 #include "kparams.h"
+#include "mem_layout.h"
 #include "wasi_impl.h"
 
 namespace wbh {
@@ -308,11 +309,7 @@ uint32_t shard_size(uint32_t n, uint32_t g_count, uint32_t part, uint32_t g);
 
 constexpr uint32_t kBlockWords = 1024;   // host-view block: 4 KiB of each of a wave's 64 lanes
 
-// Word `w` of lane `lane` within its wave's memory region, granules of 2^g words
-// (dbc_ops.h GMem): ((w >> g) * 64 + lane) * 2^g + (w & (2^g - 1)).
-inline size_t lane_word(uint64_t w, uint32_t lane, uint32_t g) {
-  return (size_t(w >> g) << (6 + g)) + (size_t(lane) << g) + size_t(w & ((1u << g) - 1u));
-}
+// (lane_word, the address of a lane's word within its wave's region: mem_layout.h)
 
 // One service round's copy of linear-memory rows across all parked waves (hostcall.cpp):
 // row b = words [64b, 64b + 64) of every lane, 16 KiB per wave, contiguous on the device
@@ -364,6 +361,11 @@ struct WaveView {
 
 uint8_t mem_rw(WasmEdge_BatchContext *C, uint32_t Inst, uint32_t Off, uint32_t Len,
                uint8_t *Dst, const uint8_t *Src);
+// bulk transfer (hostcall.cpp, mem_io.hip): rows of the [n][Stride] buffer Buf (`device`: a
+// device pointer) to (`write`) or from memory 0 of every instance of a single-device context;
+// PerInstance (host, or NULL): 0 / MemoryOutOfBounds per instance. 0 or RuntimeError.
+uint8_t mem_io(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offset, const uint32_t *Lens,
+               uint32_t Len, uint8_t *Buf, uint64_t Stride, uint8_t *PerInstance, bool write, bool device);
 // pool rows (hostcall.cpp): give wave `wave` rows up to `rows` pool pages (false: no
 // device memory for all of them; it keeps what it got); return every row at Reset
 bool pool_reserve(WasmEdge_BatchContext *C, uint32_t wave, uint32_t rows);

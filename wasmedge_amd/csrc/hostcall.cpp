@@ -21,6 +21,7 @@
 #include <thread>
 
 #include "batch_ctx.h"
+#include "mem_io.h"
 
 namespace wbh {
 
@@ -174,6 +175,122 @@ uint8_t mem_rw(WasmEdge_BatchContext *C, uint32_t Inst, uint32_t Off, uint32_t L
   // the raised write mark (LS_HWM): the next Reset re-initialises these bytes
   if (view.hwm_dirty && !C->hip_ok(hipMemcpy(mark, &hwm[lane], 4, hipMemcpyHostToDevice), "memory"))
     return kRuntimeError;
+  return 0;
+}
+
+// ---- bulk transfer (WasmEdge_BatchWriteMemories / ReadMemories) ----------------------
+// Rows of a [n][Stride] buffer <-> memory 0 of every instance, by the kernels of mem_io.hip:
+// the bound check, the status bytes and the write marks are the device's. A device buffer is
+// used where it lies; a host buffer goes through a staging buffer on the device, rows 16-byte
+// aligned (so the kernel's tiled path moves 16 bytes per thread whatever Stride is), at most
+// kStageBytes at a time.
+constexpr uint64_t kStageBytes = uint64_t(256) << 20;
+
+uint8_t mem_io(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offset, const uint32_t *Lens,
+               uint32_t Len, uint8_t *Buf, uint64_t Stride, uint8_t *PerInstance, bool write, bool device) {
+  DevScope dev(C);
+  if (!C->settle() || !pool_upload(C)) return kRuntimeError;
+  const uint32_t n = C->n;
+  if (n == 0) return 0;
+  if (device && Len) {
+    // An allocation this HIP runtime knows must be device memory of this context's device
+    // and hold NumInstances rows. One it does not know (hipMemoryTypeUnregistered: a
+    // framework that brings a HIP runtime of its own allocates there) is the caller's word.
+    hipPointerAttribute_t at{};
+    void *base = nullptr;
+    size_t size = 0;
+    const bool known = hipPointerGetAttributes(&at, Buf) == hipSuccess && at.type != hipMemoryTypeUnregistered;
+    if (!known) (void)hipGetLastError();
+    if (known && (at.type != hipMemoryTypeDevice || at.device != C->device ||
+                  hipMemGetAddressRange(&base, &size, Buf) != hipSuccess)) {
+      (void)hipGetLastError();
+      return C->fail(kRuntimeError, "memories: not a buffer on the context's device");
+    }
+    if (known) {
+      const uint64_t room = uint64_t(size) - uint64_t(Buf - static_cast<uint8_t *>(base));
+      if (room < Len || (n > 1 && Stride > (room - Len) / (n - 1)))
+        return C->fail(kRuntimeError, "memories: the device buffer is smaller than NumInstances rows");
+    }
+  }
+  DevBuf<uint32_t> d_off, d_len;
+  DevBuf<uint8_t> d_st, stage;
+  if (!d_st.alloc(n) || (Offsets && !d_off.alloc(n)) || (Lens && !d_len.alloc(n))) {
+    (void)hipGetLastError();
+    return C->fail(kRuntimeError, "memories: no device memory");
+  }
+  if ((Offsets && !C->hip_ok(hipMemcpy(d_off.ptr, Offsets, size_t(n) * 4, hipMemcpyHostToDevice), "memories")) ||
+      (Lens && !C->hip_ok(hipMemcpy(d_len.ptr, Lens, size_t(n) * 4, hipMemcpyHostToDevice), "memories")))
+    return kRuntimeError;
+  MemIoParams p{};
+  p.mem = C->mem.ptr;
+  p.lstate = C->lstate.ptr;
+  p.ptab = C->pt_w ? C->ptab.ptr : nullptr;
+  p.offsets = d_off.ptr;
+  p.lens = d_len.ptr;
+  p.status = d_st.ptr;
+  p.mem_words = C->mem_words;
+  p.mlog = C->mlog;
+  p.rpages = C->rpages;
+  p.ptab_w = C->pt_w;
+  p.ls_slots = C->ls_slots;
+  p.offset = Offset;
+  p.len = Len;
+  p.write = write ? 1 : 0;
+  auto run = [&](uint32_t first, uint32_t last, uint8_t *buf, uint64_t stride) {
+    p.first = first;
+    p.last = last;
+    p.buf = buf;
+    p.stride = stride;
+    return C->hip_ok(wb_launch_mem_io(&p, C->stream), "memories") &&
+           C->hip_ok(hipStreamSynchronize(C->stream), "memories");
+  };
+  std::vector<uint8_t> st(n, 0);
+  if (device || Len == 0) {
+    if (!run(0, n, Len ? Buf : nullptr, Len ? Stride : 0)) return kRuntimeError;
+    if (!C->hip_ok(hipMemcpy(st.data(), d_st.ptr, n, hipMemcpyDeviceToHost), "memories")) return kRuntimeError;
+  } else {
+    const uint64_t pitch = (uint64_t(Len) + 15u) & ~uint64_t(15);
+    uint64_t per = std::max<uint64_t>(1, kStageBytes / pitch);
+    if (per >= 64) per &= ~uint64_t(63);   // whole waves
+    per = std::min<uint64_t>(per, n);
+    if (!stage.alloc(size_t(per * pitch))) {
+      (void)hipGetLastError();
+      return C->fail(kRuntimeError, "memories: no device memory for the staging buffer");
+    }
+    std::vector<uint8_t> tmp;
+    const bool flat = Stride == pitch && Len == pitch;   // host rows as the staging buffer's
+    for (uint64_t first = 0; first < n; first += per) {
+      const uint32_t last = uint32_t(std::min<uint64_t>(n, first + per)), rows = last - uint32_t(first);
+      uint8_t *host = Buf + first * Stride;
+      if (write &&
+          !C->hip_ok(flat ? hipMemcpy(stage.ptr, host, size_t(rows) * pitch, hipMemcpyHostToDevice)
+                                     : hipMemcpy2D(stage.ptr, pitch, host, Stride, Len, rows, hipMemcpyHostToDevice),
+                     "memories"))
+        return kRuntimeError;
+      if (!run(uint32_t(first), last, stage.ptr, pitch)) return kRuntimeError;
+      if (!C->hip_ok(hipMemcpy(st.data() + first, d_st.ptr + first, rows, hipMemcpyDeviceToHost), "memories"))
+        return kRuntimeError;
+      if (write) continue;
+      // a read fills bytes [0, len_i) of the rows in bounds and leaves every other byte of
+      // Dst as it is: in one copy when that is every row's first Len bytes
+      bool whole = !Lens;
+      for (uint32_t i = uint32_t(first); i < last && whole; i++) whole = st[i] == 0;
+      if (whole) {
+        if (!C->hip_ok(flat ? hipMemcpy(host, stage.ptr, size_t(rows) * pitch, hipMemcpyDeviceToHost)
+                                       : hipMemcpy2D(host, Stride, stage.ptr, pitch, Len, rows, hipMemcpyDeviceToHost),
+                       "memories"))
+          return kRuntimeError;
+        continue;
+      }
+      tmp.resize(size_t(rows) * pitch);
+      if (!C->hip_ok(hipMemcpy(tmp.data(), stage.ptr, tmp.size(), hipMemcpyDeviceToHost), "memories"))
+        return kRuntimeError;
+      for (uint32_t i = uint32_t(first); i < last; i++)
+        if (st[i] == 0)
+          memcpy(Buf + uint64_t(i) * Stride, tmp.data() + (i - first) * pitch, Lens ? std::min(Lens[i], Len) : Len);
+    }
+  }
+  if (PerInstance) memcpy(PerInstance, st.data(), n);
   return 0;
 }
 

@@ -251,6 +251,35 @@ WasmEdge_Result results(Ctx *C, WasmEdge_Value *rets, uint32_t rlen, uint8_t *st
   });
 }
 
+// Bulk transfer with a host buffer: each shard gets its instances' offsets, lengths and rows
+// (packed, Len bytes apart) by the placement, and gives back their status bytes and, on a
+// read, their rows -- which start out as the caller's, so that what an instance does not
+// fill stays as it was.
+WasmEdge_Result mem_io(Ctx *C, const uint32_t *offsets, uint32_t offset, const uint32_t *lens, uint32_t len,
+                       uint8_t *buf, uint64_t stride, uint8_t *per, bool write) {
+  std::vector<uint32_t> fo, fl;
+  std::vector<uint8_t> rows, st;
+  return each(C, [&](Ctx *s) {
+    fo.assign(offsets ? s->n : 0, 0);
+    fl.assign(lens ? s->n : 0, 0);
+    rows.resize(size_t(s->n) * len);
+    st.assign(s->n, 0);
+    for (uint32_t i = 0; i < s->n; i++) {
+      const uint32_t g = s->gid(i);
+      if (offsets) fo[i] = offsets[g];
+      if (lens) fl[i] = lens[g];
+      if (len) memcpy(rows.data() + size_t(i) * len, buf + uint64_t(g) * stride, len);
+    }
+    const WasmEdge_Result r = R(wbh::mem_io(s, offsets ? fo.data() : nullptr, offset, lens ? fl.data() : nullptr,
+                                            len, rows.data(), len, st.data(), write, false));
+    if (r.Code) return r;
+    for (uint32_t i = 0; i < s->n && !write && len; i++)
+      memcpy(buf + uint64_t(s->gid(i)) * stride, rows.data() + size_t(i) * len, len);
+    if (per) scatter(s, st.data(), per, 1, 1);
+    return R(0);
+  });
+}
+
 // [n] u64 outputs (hashes, costs)
 WasmEdge_Result gather_u64(Ctx *C, uint64_t *out, WasmEdge_Result (*f)(Ctx *, uint64_t *)) {
   std::vector<uint64_t> v;

@@ -20,6 +20,10 @@ WasmEdge_Result reset(WasmEdge_BatchContext *C, double *secs);
 WasmEdge_Result run(WasmEdge_BatchContext *C, double *secs);
 WasmEdge_Result results(WasmEdge_BatchContext *C, WasmEdge_Value *rets, uint32_t rlen, uint8_t *st,
                         uint64_t *cnt);
+// bulk transfer with a host buffer: Offsets / Lens / rows sliced, PerInstance gathered
+WasmEdge_Result mem_io(WasmEdge_BatchContext *C, const uint32_t *offsets, uint32_t offset,
+                       const uint32_t *lens, uint32_t len, uint8_t *buf, uint64_t stride, uint8_t *per,
+                       bool write);
 WasmEdge_Result gather_u64(WasmEdge_BatchContext *C, uint64_t *out,
                            WasmEdge_Result (*f)(WasmEdge_BatchContext *, uint64_t *));
 // every shard (stops at the first failure)
