@@ -159,7 +159,7 @@ struct Em {
   uint32_t seq[256] = {};
   uint32_t nvm = 0;
   uint32_t basev = 122;   // the current access group's base pair (BASE or v[124:125])
-  struct Stub { std::string lab; uint32_t pc, done; uint64_t cdone; };
+  struct Stub { std::string lab; uint32_t pc, done; uint64_t cdone; std::string fix; };   // fix: def_fix() there
   std::vector<Stub> stubs;
   const struct MemGroup *group = nullptr;   // set on a group's first access (group_check)
   uint32_t fb = 0;                          // frame base (Program::global_cells)
@@ -185,13 +185,68 @@ struct Em {
   // (and cells whose value is a forwarded word read straight from its VGPR until they
   // are written: amap cell -> VGPR)
   std::map<uint32_t, uint32_t> amap;
+  // Constant and copy propagation (kprop; emit_prop below): a CONST32 or MOV32 writes
+  // nothing -- its cell is deferred, a known constant or another VGPR's value, under the
+  // cell's own VGPR number (shifted cells of an inlined callee and its caller share the
+  // map). The plain 32-bit ops emit_prop compiles read a deferred cell as a constant
+  // operand or through the other VGPR; before anything else every deferred cell gets its
+  // register (def_flush), a leave stub writes the cells deferred where it leaves
+  // (Stub::fix), and a VGPR that changes is first copied to the cells that name it
+  // (before_write). A deferred cell never names the own register of a deferred cell.
+  struct Def { bool k; uint32_t v; };   // k: the constant v, else VGPR v
+  std::map<uint32_t, Def> def;
+  bool kprop = false;
+  uint32_t own(uint32_t c) const { return 128 + sc(c); }
+  bool konst(uint32_t c, uint32_t *k) const {   // cell c is a deferred constant
+    if (def.empty() || int64_t(c) == alias_cell || amap.count(c)) return false;
+    auto it = def.find(own(c));
+    if (it == def.end() || !it->second.k) return false;
+    *k = it->second.v;
+    return true;
+  }
   std::string V(uint32_t c) const {
     if (int64_t(c) == alias_cell) return "v" + std::to_string(alias_reg);
     if (!amap.empty()) {
       auto it = amap.find(c);
       if (it != amap.end()) return "v" + std::to_string(it->second);
     }
+    if (!def.empty()) {
+      auto it = def.find(own(c));
+      // (a deferred constant has no register: its readers ask konst first -- else no assembly)
+      if (it != def.end()) return it->second.k ? "v_deferred_constant" : "v" + std::to_string(it->second.v);
+    }
     return "v" + std::to_string(128 + sc(c));
+  }
+  // a cell as the source of a v_mov_b32 or as src0 of a VOP2 _e32 (a literal is fine there)
+  std::string sv(uint32_t c) const {
+    uint32_t k;
+    char buf[16];
+    if (!konst(c, &k)) return V(c);
+    snprintf(buf, sizeof buf, "0x%x", k);
+    return buf;
+  }
+  void def_mat(uint32_t reg) {   // the deferred cell with own register `reg` gets its value
+    auto it = def.find(reg);
+    if (it == def.end()) return;
+    if (it->second.k) l("v_mov_b32 v%u, 0x%x", reg, it->second.v);
+    else l("v_mov_b32 v%u, v%u", reg, it->second.v);
+    def.erase(it);
+  }
+  void def_flush(uint32_t below = ~0u) {   // ... every one (whose register is below `below`)
+    for (auto it = def.begin(); it != def.end() && it->first < below;) {
+      const uint32_t reg = (it++)->first;
+      def_mat(reg);
+    }
+  }
+  std::string def_fix() const {   // the same writes as text, for a leave stub
+    std::string s;
+    char buf[64];
+    for (const auto &kv : def) {
+      if (kv.second.k) snprintf(buf, sizeof buf, "v_mov_b32 v%u, 0x%x\n", kv.first, kv.second.v);
+      else snprintf(buf, sizeof buf, "v_mov_b32 v%u, v%u\n", kv.first, kv.second.v);
+      s += buf;
+    }
+    return s;
   }
   void materialize(uint32_t c) {   // the cell's own register gets its aliased value
     auto it = amap.find(c);
@@ -204,6 +259,16 @@ struct Em {
     for (const auto &kv : amap)
       if (kv.second == reg) cells.push_back(kv.first);
     for (uint32_t c : cells) materialize(c);
+    cells.clear();
+    for (const auto &kv : def)
+      if (!kv.second.k && kv.second.v == reg) cells.push_back(kv.first);
+    for (uint32_t r : cells) def_mat(r);
+  }
+  // cell c is about to be written (its sources already read): what it held goes
+  void cell_written(uint32_t c) {
+    before_write(own(c));
+    def.erase(own(c));
+    amap.erase(c);
   }
   std::string P(uint32_t c) const {
     return "v[" + std::to_string(128 + sc(c)) + ":" + std::to_string(129 + sc(c)) + "]";
@@ -382,7 +447,7 @@ struct Em {
   // a leave stub before instruction pc without a test here (the caller branches to it)
   std::string leave_stub() {
     const std::string lab = "Lx" + std::to_string(run) + "_" + std::to_string(stubs.size());
-    stubs.push_back(Stub{lab, pc, done, cdone});
+    stubs.push_back(Stub{lab, pc, done, cdone, def_fix()});
     return lab;
   }
   // A run that starts with a POST_CALL and ends with a CALL checks the call stack once at
@@ -473,7 +538,7 @@ struct MemGroup {
 void group_base(Em &e, const MemGroup &G) {
   if (e.g != 0) return;
   const std::string bp = e.base();
-  e.l("v_mov_b32 %s, %s", W0, e.v(G.base));
+  e.l("v_mov_b32 %s, %s", W0, e.sv(G.base).c_str());
   e.l("v_lshlrev_b64 %s, 6, %s", bp.c_str(), WP);
   e.l("v_lshl_add_u64 %s, %s, 0, %s", bp.c_str(), bp.c_str(), MEM);
 }
@@ -789,11 +854,197 @@ bool emit_xmem(Em &e, const DInstr &I) {
   return true;
 }
 
+// ---------------------------------------------------------------- constant and copy propagation
+// (Em::def) The ops that defer their result or read deferred cells: constants, copies and
+// the plain 32-bit integer ops of hash rounds. None of them can leave the run. A constant
+// operand is a literal in src0 of a VOP2 _e32; VOP3 (v_add3_u32, v_alignbit_b32) takes an
+// inline constant (-16..64) only. x ^ 0, x + 0, x | 0 are copies of x; ops on constants
+// alone are constants.
+bool prop_op(uint16_t op) {
+  switch (op) {
+    case OP_CONST32: case OP_MOV32: case OP_I32_ADD: case OP_I32_OR: case OP_I32_XOR:
+    case OP_I32_ADD_I: case OP_I32_OR_I: case OP_I32_XOR_I: case OP_I32_ROTR_I:
+    case OP_I32_ROTL_I: case OP_I32_ADD3: case OP_I32_XOR_ROTR_I: case OP_I32_XOR_ROTL_I:
+    case OP_I32_ADD_XROTR_I: case OP_I32_ADD3_XROTR_I:
+      return true;
+    default:
+      return false;
+  }
+}
+bool inline_k(uint32_t k) { return int32_t(k) >= -16 && int32_t(k) <= 64; }
+uint32_t rotr32(uint32_t x, uint32_t k) { return (k & 31u) ? (x >> (k & 31u)) | (x << (32u - (k & 31u))) : x; }
+
+// the register a one-result op writes for cell c (a forwarded store's value: its word's
+// VGPR, Em::alias_cell); what the cell held goes. Call it after the sources are read.
+std::string prop_dst(Em &e, uint32_t c) {
+  if (int64_t(c) == e.alias_cell) {
+    e.def.erase(e.own(c));
+    e.amap.erase(c);
+    return "v" + std::to_string(e.alias_reg);
+  }
+  e.cell_written(c);
+  return "v" + std::to_string(e.own(c));
+}
+void prop_const(Em &e, uint32_t c, uint32_t k) {   // c = k
+  if (int64_t(c) == e.alias_cell) {
+    e.l("v_mov_b32 %s, 0x%x", prop_dst(e, c).c_str(), k);
+    return;
+  }
+  e.cell_written(c);
+  e.def[e.own(c)] = Em::Def{true, k};
+}
+void prop_copy(Em &e, uint32_t c, const std::string &r) {   // c = the value in VGPR r ("v<n>")
+  const uint32_t reg = uint32_t(atoi(r.c_str() + 1));
+  if (int64_t(c) == e.alias_cell) {
+    e.l("v_mov_b32 %s, %s", prop_dst(e, c).c_str(), r.c_str());
+    return;
+  }
+  if (reg == e.own(c)) return;   // (only a written cell's register is named: c holds it)
+  e.cell_written(c);
+  e.def[e.own(c)] = Em::Def{false, reg};
+}
+
+// false: this shape has no form here (emit flushes and compiles it as ever)
+bool emit_prop(Em &e, const DInstr &I) {
+  const uint16_t op = op_of(I);
+  const uint32_t a = I.w1 & 0xFFFFu, b = I.w1 >> 16, c = I.w2 & 0xFFFFu, d = I.w2 >> 16, imm = I.w3;
+  uint32_t ka = 0, kb = 0;
+  switch (op) {
+    case OP_CONST32:
+      e.sync({c});
+      prop_const(e, c, imm);
+      return true;
+    case OP_MOV32:
+      e.sync({a, c});
+      if (a == c) return true;
+      if (e.konst(a, &ka)) prop_const(e, c, ka);
+      else prop_copy(e, c, e.V(a));
+      return true;
+    case OP_I32_ADD: case OP_I32_OR: case OP_I32_XOR:
+    case OP_I32_ADD_I: case OP_I32_OR_I: case OP_I32_XOR_I: {
+      const bool ri = op == OP_I32_ADD_I || op == OP_I32_OR_I || op == OP_I32_XOR_I;
+      const bool add = op == OP_I32_ADD || op == OP_I32_ADD_I, orr = op == OP_I32_OR || op == OP_I32_OR_I;
+      const char *ins = add ? "v_add_u32_e32" : orr ? "v_or_b32_e32" : "v_xor_b32_e32";
+      if (ri) e.sync({a, c});
+      else e.sync({a, b, c});
+      const bool ca = e.konst(a, &ka);
+      bool cb = true;
+      if (ri) kb = imm;
+      else cb = e.konst(b, &kb);
+      if (ca && cb) {
+        prop_const(e, c, add ? ka + kb : orr ? (ka | kb) : (ka ^ kb));
+      } else if (ca || cb) {
+        const uint32_t k = ca ? ka : kb;
+        const std::string x = e.V(ca ? b : a);
+        if (k == 0) {
+          prop_copy(e, c, x);
+        } else {
+          const std::string dst = prop_dst(e, c);
+          e.l("%s %s, 0x%x, %s", ins, dst.c_str(), k, x.c_str());
+        }
+      } else {
+        const std::string x = e.V(a), y = e.V(b), dst = prop_dst(e, c);
+        e.l("%s %s, %s, %s", ins, dst.c_str(), x.c_str(), y.c_str());
+      }
+      return true;
+    }
+    case OP_I32_ROTR_I: case OP_I32_ROTL_I: {
+      e.sync({a, c});
+      const uint32_t k = op == OP_I32_ROTR_I ? imm & 31u : (32u - (imm & 31u)) & 31u;
+      if (e.konst(a, &ka)) {
+        prop_const(e, c, rotr32(ka, k));
+      } else {
+        const std::string x = e.V(a), dst = prop_dst(e, c);
+        e.l("v_alignbit_b32 %s, %s, %s, %u", dst.c_str(), x.c_str(), x.c_str(), k);
+      }
+      return true;
+    }
+    case OP_I32_XOR_ROTR_I: case OP_I32_XOR_ROTL_I: {
+      e.sync({a, b, c});
+      const uint32_t k = op == OP_I32_XOR_ROTR_I ? imm & 31u : (32u - (imm & 31u)) & 31u;
+      const bool ca = e.konst(a, &ka), cb = e.konst(b, &kb);
+      if (ca && cb) {
+        prop_const(e, c, rotr32(ka ^ kb, k));
+        return true;
+      }
+      const std::string x = ca ? "" : e.V(a), y = cb ? "" : e.V(b), dst = prop_dst(e, c);
+      if (ca || cb) {
+        const std::string &r = ca ? y : x;
+        if ((ca ? ka : kb) == 0) {
+          e.l("v_alignbit_b32 %s, %s, %s, %u", dst.c_str(), r.c_str(), r.c_str(), k);
+          return true;
+        }
+        e.l("v_xor_b32_e32 %s, 0x%x, %s", dst.c_str(), ca ? ka : kb, r.c_str());
+      } else {
+        e.l("v_xor_b32_e32 %s, %s, %s", dst.c_str(), x.c_str(), y.c_str());
+      }
+      e.l("v_alignbit_b32 %s, %s, %s, %u", dst.c_str(), dst.c_str(), dst.c_str(), k);
+      return true;
+    }
+    case OP_I32_ADD3: case OP_I32_ADD_XROTR_I: case OP_I32_ADD3_XROTR_I: {
+      // s = the sum of the register operands and of the constants' total ks; (XROTR) c = s,
+      // then y = rotr(y ^ s, k) with y read after c is written (c != y here)
+      const bool plain = op == OP_I32_ADD3, three = op != OP_I32_ADD_XROTR_I;
+      const uint32_t y = plain ? c : op == OP_I32_ADD3_XROTR_I ? imm & 0xFFFFu : d;
+      const uint32_t k = (op == OP_I32_ADD3_XROTR_I ? imm >> 16 : imm) & 31u;
+      if (!plain && (c == y || e.alias_cell >= 0)) return false;
+      if (plain) e.sync({a, b, c, d});
+      else e.sync({a, b, c, d, y});
+      std::vector<std::string> r;
+      uint32_t ks = 0;
+      for (uint32_t x : {a, b, d}) {
+        if (x == d && !three) break;
+        if (e.konst(x, &ka)) ks += ka;
+        else r.push_back(e.V(x));
+      }
+      if (plain && r.empty()) {
+        prop_const(e, c, ks);
+        return true;
+      }
+      if (plain && r.size() == 1 && !ks) {
+        prop_copy(e, c, r[0]);
+        return true;
+      }
+      if (r.empty() || (r.size() == 1 && !ks)) return false;
+      const std::string s = prop_dst(e, c);
+      if (r.size() == 3) {
+        e.l("v_add3_u32 %s, %s, %s, %s", s.c_str(), r[0].c_str(), r[1].c_str(), r[2].c_str());
+      } else if (r.size() == 1) {
+        e.l("v_add_u32_e32 %s, 0x%x, %s", s.c_str(), ks, r[0].c_str());
+      } else if (ks && inline_k(ks)) {
+        e.l("v_add3_u32 %s, %s, %s, %d", s.c_str(), r[0].c_str(), r[1].c_str(), int32_t(ks));
+      } else {
+        e.l("v_add_u32_e32 %s, %s, %s", s.c_str(), r[0].c_str(), r[1].c_str());
+        if (ks) e.l("v_add_u32_e32 %s, 0x%x, %s", s.c_str(), ks, s.c_str());
+      }
+      if (plain) return true;
+      const bool cy = e.konst(y, &kb);
+      const std::string ys = cy ? "" : e.V(y), yd = prop_dst(e, y);
+      if (cy && kb == 0) {
+        e.l("v_alignbit_b32 %s, %s, %s, %u", yd.c_str(), s.c_str(), s.c_str(), k);
+        return true;
+      }
+      if (cy) e.l("v_xor_b32_e32 %s, 0x%x, %s", yd.c_str(), kb, s.c_str());
+      else e.l("v_xor_b32_e32 %s, %s, %s", yd.c_str(), ys.c_str(), s.c_str());
+      e.l("v_alignbit_b32 %s, %s, %s, %u", yd.c_str(), yd.c_str(), yd.c_str(), k);
+      return true;
+    }
+    default:
+      return false;
+  }
+}
+
 // ---------------------------------------------------------------- one instruction
 // Returns false when the instruction has no compiled form (the run ends before it).
 bool emit(Em &e, const DInstr &I) {
   const uint16_t op = op_of(I);
   const uint32_t a = I.w1 & 0xFFFFu, b = I.w1 >> 16, c = I.w2 & 0xFFFFu, d = I.w2 >> 16, imm = I.w3;
+  if (e.kprop) {
+    if (prop_op(op) && emit_prop(e, I)) return true;
+    e.def_flush();   // anything else reads and writes the cells' own registers
+    if (prop_op(op))
+      while (!e.amap.empty()) e.materialize(e.amap.begin()->first);
+  }
   // i32 binary ops: (register form, immediate form); SUB_I as a - imm
   struct Bin { uint16_t rr, ri; const char *ins; int form; };   // form 0 VOP2, 1 shift, 2 VOP3
   static const Bin bins[] = {
@@ -1527,6 +1778,7 @@ void emit_batch(Em &e, const Program &P, uint32_t rpc, const LoadBatch &b,
   std::vector<uint32_t> bv(b.i1 - b.i0, 122);
   uint32_t groups = 0;
   e.pc = rpc + b.i0;
+  e.def_flush();   // (the checks name the address cells' registers)
   for (uint32_t k = b.i0; k < b.i1; k++) {
     if (lead[k] >= 0) {
       e.basev = groups++ ? 124 : 122;
@@ -2337,16 +2589,20 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
 // word in a VGPR above every cell (F); the inlined call's end goes on in a copy of Pp
 // (suffix p) whose taken branch enters a copy of R (suffix c) where the callee's loads
 // are moves from F: no loads, hence no waits behind the previous trip's stores (vmcnt
-// retires in issue order). Stores stay real (memory is always current) and a copy's
-// lanes are the group that ran the trip before (the fast path keeps exec), so every
-// lane's F words are its own memory's. The c copy skips the load-only groups' checks:
-// the first trip, in R, checked the same constant addresses and memory never shrinks.
+// retires in issue order). R's stores are real; the c copy's only update F (the words are
+// dirty) and every way out of the c / p pair but the back edge stores the dirty words
+// first (RunCompile::flush_dirty; WB_FWD_LAZY=0: the copy stores every trip), so memory
+// is current wherever it can be observed. A copy's lanes are the group that ran the trip
+// before (the fast path keeps exec), so every lane's F words are its own memory's. The c
+// copy skips the groups' checks: the first trip, in R, checked the same constant
+// addresses and raised the write mark, and memory never shrinks.
 struct FwdPlan {
   size_t post = 0;                                       // Pp (run index)
   std::vector<int64_t> addr;                             // callee body index -> address
   std::map<uint32_t, uint32_t> freg;                     // address -> VGPR
   std::vector<std::pair<uint32_t, uint32_t>> end_copy;   // (VGPR, physical cell)
   std::vector<uint8_t> copy_now;   // body index: a load whose cell changes later (copy at once)
+  std::vector<uint32_t> dirty;     // the addresses the callee stores to, ascending
 };
 
 bool fwd_plan(const Program &P, const std::vector<JitRun> &runs, size_t k, size_t f, size_t post,
@@ -2391,6 +2647,10 @@ bool fwd_plan(const Program &P, const std::vector<JitRun> &runs, size_t k, size_
     }
     step(I, off);
   }
+  for (uint32_t i = 0; i + 1 < F.len; i++)
+    if (op_of(P.code[F.pc + i]) == OP_ST32) out->dirty.push_back(uint32_t(out->addr[i]));
+  std::sort(out->dirty.begin(), out->dirty.end());
+  out->dirty.erase(std::unique(out->dirty.begin(), out->dirty.end()), out->dirty.end());
   uint32_t prev = 0;
   bool first = true;
   for (auto &kv : lastacc) {   // (ordered) distinct words must not overlap
@@ -3821,6 +4081,9 @@ JitKnobs jit::read_knobs() {
   k.fwd = on("WB_FWD");
   k.fwd_store = on("WB_FWD_STORE");
   k.fwd_alias = on("WB_FWD_ALIAS");
+  k.kprop = on("WB_KPROP");
+  k.fwd_lazy = on("WB_FWD_LAZY");
+  k.fwd_loop = on("WB_FWD_LOOP");
   k.ret_pf = on("WB_RET_PF");
   k.brt_thread = on("WB_BRT_THREAD");
   k.trip_fwd = on("WB_TRIP_FWD");
@@ -3977,6 +4240,7 @@ struct RunCompile {
   uint32_t fuse_cell = ~0u;
   bool cmp_any = false;
   int lab = 0, nfast = 0;
+  size_t head_stubs = 0;   // the leave stubs of the code before Lpa
 
   RunCompile(const SimtCtx &c, size_t k_, int var_)
       : t(c.t), kn(c.kn), ix(c.ix), runs(c.runs), pl(c.pl), P(c.t.P), cost(c.t.cost), nob(c.nob),
@@ -3985,7 +4249,58 @@ struct RunCompile {
         last(P.code[r.pc + r.len - 1]), lop(op_of(last)), fall(r.pc + r.len),
         tgt((lop == OP_CALL || lop == OP_TAIL_CALL || is_branch_op(lop)) ? last.w3 : 0),
         // (stub labels apart)
-        e(c.t, uint32_t(k_ + size_t(var_) * 2 * c.runs.size()), c.nob.empty() ? nullptr : &c.nob) {}
+        e(c.t, uint32_t(k_ + size_t(var_) * 2 * c.runs.size()), c.nob.empty() ? nullptr : &c.nob) {
+    e.kprop = kn.kprop;
+    // the forwarding loop this job belongs to: its run R (every var of R, and Pp's copy)
+    auto lo = pl.loop_of.find(k);
+    const size_t R = var == 2 && lo != pl.loop_of.end() ? lo->second : k;
+    auto fp = pl.plans.find(R);
+    if (fp != pl.plans.end() && (var != 2 || lo != pl.loop_of.end())) {
+      loop = &fp->second;
+      lazy = kn.fwd_lazy && kn.fwd_store && var != 0 && !loop->dirty.empty();
+      tight = kn.fwd_loop;
+      if (tight && var == 2) pre_cnt = runs[R].cnt + runs[size_t(pl.inl_f[R])].cnt;
+    }
+  }
+
+  // Forwarding loops (FwdPlan). lazy: copy c's forwarded stores only update F, and every
+  // way out of the c / p pair but the back edge first stores the dirty words (flush_dirty).
+  // tight: c drops its loop-invariant stack check and falls through into p's code past
+  // the POST_CALL (p has no other entry: its head is not emitted, c's out-of-line code
+  // follows p's: `cold`), and R and c leave the inlined call's count to p's ways out
+  // (pre_cnt), which add it with their own.
+  const FwdPlan *loop = nullptr;
+  bool lazy = false, tight = false;
+  uint32_t pre_cnt = 0;
+  std::string cold, callee_cold;   // (callee_cold: an inlined callee's out-of-line code)
+
+  // The dirty words (F registers) to memory, under the current exec (the lanes that ran
+  // the trip): vector code only -- no scalar register, SCC or VCC changes. R raised the
+  // write mark and checked the bounds for these constant addresses on the first trip.
+  std::string flush_dirty() const {
+    if (!lazy) return "";
+    Em d(t);
+    uint32_t a0 = 0;
+    bool open = false;
+    for (uint32_t A : loop->dirty) {
+      const uint32_t fr = loop->freg.at(A);
+      if (t.glog == 0) {   // word interleave: MEM + A * 64, 4095 bytes of offset per base
+        if (!open || uint64_t(A - a0) * 64u > 4095) {
+          d.l("v_mov_b32 %s, 0x%x", W0, A);
+          d.l("v_lshlrev_b64 v[122:123], 6, %s", WP);
+          d.l("v_lshl_add_u64 v[122:123], v[122:123], 0, %s", MEM);
+          a0 = A;
+          open = true;
+        }
+        d.l("global_store_dword v[122:123], v%u, off offset:%u", fr, (A - a0) * 64u);
+      } else {
+        d.l("v_mov_b32 %s, 0x%x", Y0, A);
+        granule_addr(d, XP, Y0, MEM);
+        d.l("global_store_dword %s, v%u, off", XP, fr);
+      }
+    }
+    return d.o;
+  }
 
   // a forwarding loop's post-call copy enters its run's forwarding copy
   const char *copy_sfx(size_t q) const {
@@ -4111,10 +4426,20 @@ struct RunCompile {
       e.done += (I.w0 >> 16) & 0xFFu;
       if (cost) e.cdone += cost->full(P, r.pc + i);
       // an inlined call goes on here, after the POST_CALL it makes unnecessary
-      if (i == 0 && op_of(I) == OP_POST_CALL) e.l("Lpa%s:", K.c_str());
+      if (i == 0 && op_of(I) == OP_POST_CALL) {
+        e.l("Lpa%s:", K.c_str());
+        head_stubs = e.stubs.size();
+      }
     }
+    // deferred cells get their registers where the run ends; an inlined call's arguments
+    // (cells from L on) stay deferred into the callee's code
+    e.def_flush(pl.inl_f[k] >= 0 ? 128 + (last.w1 & 0xFFFFu) : ~0u);
     e.drain();
     if (kn.jit_sched) e.o = e.o.substr(0, body_at) + schedule(e.o.substr(body_at), kn);
+    if (tight && var == 2) {   // (entered past the POST_CALL only)
+      e.o = e.o.substr(e.o.find("Lpa" + K + ":\n"));
+      e.stubs.erase(e.stubs.begin(), e.stubs.begin() + long(head_stubs));
+    }
     e.pc = r.pc + r.len - 1;
     e.group = nullptr;
     return true;
@@ -4137,6 +4462,7 @@ struct RunCompile {
                              copy_sfx(it->second);
       long_jump(e, tl, q);
       e.l("%s:", disp.c_str());
+      e.o += flush_dirty();
       banks = false;
     }
     e.l("s_waitcnt lgkmcnt(0)");
@@ -4189,7 +4515,7 @@ struct RunCompile {
   }
   void fallthrough(uint32_t cnt) {   // next(): stop at the lowest waiting pc
     e.gas_add(c_fall);
-    e.l("s_add_u32 s65, s65, 0x%x", cnt);
+    e.l("s_add_u32 s65, s65, 0x%x", cnt + pre_cnt);
     fast_to(fall, false, false);
     e.l("s_mov_b32 s62, 0x%x", fall * 32u);
     e.l("s_cmp_ge_u32 s62, s63");
@@ -4208,14 +4534,24 @@ struct RunCompile {
     const std::string IK = "i" + K;
     // the real call's LDS check first: a call that would pass the LDS part of the call
     // stack leaves before the CALL (the C++ step makes it), as without inlining
-    e.l("v_add_u32_e32 %s, %u, v102", X0, n + 1);
-    e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
-    e.leave_if_t2();
+    // (not in a tight loop's copy c: it is entered only from p's code past the POST_CALL,
+    // which only R's and c's inlined calls reach, so R made this check on the first trip --
+    // and nothing in R, the callee or Pp moves the stack height v102 or the limit s93)
+    if (!(tight && var == 1)) {
+      e.l("v_add_u32_e32 %s, %u, v102", X0, n + 1);
+      e.l("v_cmp_lt_u32_e64 %s, s93, %s", T2, X0);
+      e.leave_if_t2();
+    }
     const std::vector<uint8_t> dead = dead_zeros(P, rf);
     // (labels apart from every real run's; counted before the callee: the caller's run)
     Em ei = e.inlined(e.run + uint32_t(runs.size()), off, r.cnt);
+    ei.kprop = e.kprop;
+    ei.def.swap(e.def);   // (the arguments)
     for (uint32_t q = 0; q < nloc; q++)
-      if (dead.empty() || !dead[fb + nargs + q]) ei.l("v_mov_b32 %s, 0", ei.v(fb + nargs + q));
+      if (dead.empty() || !dead[fb + nargs + q]) {
+        if (ei.kprop) prop_const(ei, fb + nargs + q, 0);
+        else ei.l("v_mov_b32 %s, 0", ei.v(fb + nargs + q));
+      }
     std::vector<int> lead2;
     const std::vector<MemGroup> groups2 = jit_groups(P, rf, &lead2);
     const size_t body2 = ei.o.size();
@@ -4246,16 +4582,19 @@ struct RunCompile {
       const int64_t fa = fwd ? fwd->addr[i] : -1;
       if (fa >= 0 && fc && op_of(I) == OP_LD32) {
         // (a group that also stores still computes its base: its stores use it)
-        if (ei.group && ei.group->store_end) group_base(ei, *ei.group);
+        if (ei.group && ei.group->store_end && !lazy) group_base(ei, *ei.group);
         ei.group = nullptr;
         const uint32_t c = I.w2 & 0xFFFFu;
         ei.sync({c});
+        ei.cell_written(c);
         if (kn.fwd_alias) ei.amap[c] = fwd->freg.at(uint32_t(fa));
         else ei.l("v_mov_b32 %s, v%u", ei.v(c), fwd->freg.at(uint32_t(fa)));
         ei.done += (I.w0 >> 16) & 0xFFu;
         continue;
       }
-      if (!ei.amap.empty() && !(fa >= 0 && op_of(I) == OP_ST32 && kn.fwd_store)) {
+      // (emit_prop's ops read aliased cells where they are and end the aliases themselves)
+      if (!ei.amap.empty() && !(fa >= 0 && op_of(I) == OP_ST32 && kn.fwd_store) &&
+          !(ei.kprop && prop_op(op_of(I)))) {
         // an aliased cell this instruction writes gets its own register back first if
         // the instruction also reads it (else the alias just ends); anything but a plain
         // 32-bit op (which might leave, or names register pairs) gets every cell back
@@ -4281,9 +4620,15 @@ struct RunCompile {
         ei.before_write(fwd->freg.at(uint32_t(fa)));
         if (renamed != int64_t(I.w1 >> 16)) {
           ei.sync({I.w1 >> 16});
-          ei.l("v_mov_b32 %s, %s", fr.c_str(), ei.v(I.w1 >> 16));
+          ei.l("v_mov_b32 %s, %s", fr.c_str(), ei.sv(I.w1 >> 16).c_str());
         }
         renamed = -1;
+        if (fc && lazy) {   // the word is dirty: p's ways out store it (flush_dirty)
+          ei.group = nullptr;
+          ei.done += (I.w0 >> 16) & 0xFFu;
+          continue;
+        }
+        ei.def_mat(ei.own(I.w1 & 0xFFFFu));   // (the address cell's register is read)
         if (fc) {   // (the first trip checked these constant addresses, raised the mark)
           if (ei.group) group_base(ei, *ei.group);
           ei.group = nullptr;
@@ -4372,10 +4717,16 @@ struct RunCompile {
     // the caller's POST_CALL (its run's banks as that run would have loaded them)
     const DInstr &rt = P.code[rf.pc + rf.len - 1];
     const uint32_t ra = rt.w1 & 0xFFFFu, nres = rt.w1 >> 16;
-    for (uint32_t q = 0; q < nres; q++)
-      ei.l("v_mov_b32 v%u, %s", 128 + L + q, ei.v(ra + q));
+    ei.def_flush(128 + L);   // (globals the callee set)
+    for (uint32_t q = 0; q < nres; q++) {
+      const std::string from = ei.sv(ra + q);
+      ei.before_write(128 + L + q);
+      ei.def.erase(128 + L + q);
+      ei.l("v_mov_b32 v%u, %s", 128 + L + q, from.c_str());
+    }
     ei.amap.clear();   // (the callee's cells are dead once its results are out)
-    ei.l("s_add_u32 s65, s65, 0x%x", r.cnt + rf.cnt);
+    ei.def.clear();
+    if (!(tight && fwd)) ei.l("s_add_u32 s65, s65, 0x%x", r.cnt + rf.cnt);
     {
       const JitRun &rp = runs[size_t(inl_post)];
       const DInstr &pl = P.code[rp.pc + rp.len - 1];
@@ -4390,7 +4741,8 @@ struct RunCompile {
       }
     }
     ei.l("s_mov_b32 s62, 0x%x", (callpc + 1) * 32u);
-    long_jump(ei, "Lpa" + std::to_string(inl_post) + (fwd ? "p" : ""), "Lpq" + IK);
+    if (!(tight && var == 1))   // (c falls through into p's code)
+      long_jump(ei, "Lpa" + std::to_string(inl_post) + (fwd ? "p" : ""), "Lpq" + IK);
     // leaves inside the callee: make the call real first
     std::string deopt;
     {
@@ -4404,17 +4756,18 @@ struct RunCompile {
       for (uint32_t c = fb; c < P.total_cells(); c++) d.l("v_mov_b32 v%u, v%u", 128 + c, 128 + c + off);
       deopt = d.o;
     }
-    ei.o += ei.tail;
-    for (const auto &st : ei.stubs) {
-      ei.o += st.lab + ":\n" + deopt;
+    // the callee's code follows the caller's (falls through into it; its block counts
+    // the caller's run), its out-of-line code the run's (finish)
+    e.l("Li%s:", IK.c_str());
+    e.o += ei.o;
+    ei.o = ei.tail;
+    for (const auto &st : ei.stubs) {   // (deferred cells and dirty words first)
+      ei.o += st.lab + ":\n" + st.fix + flush_dirty() + deopt;
       ei.l("s_mov_b32 s62, 0x%x", st.pc * 32u);
       ei.l("s_add_u32 s65, s65, 0x%x", st.done);
       ei.l("s_setpc_b64 s[70:71]");
     }
-    // the callee's code follows the caller's (falls through into it; its block counts
-    // the caller's run)
-    e.l("Li%s:", IK.c_str());
-    e.o += ei.o;
+    callee_cold = ei.o;
     return true;
   }
   void tail_tail_call() {
@@ -4558,7 +4911,7 @@ struct RunCompile {
       extra += x.o;
     } else {
       const std::string lab_split = "Lx" + K + "_" + std::to_string(e.stubs.size());
-      e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone});
+      e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone, e.def_fix()});
       e.l("s_cbranch_scc1 %s", lab_split.c_str());
     }
     e.l("s_lshl_b32 s62, s68, 5");
@@ -4592,6 +4945,7 @@ struct RunCompile {
         e.l("s_cbranch_scc0 Lbs%s", K.c_str());
         Em x(t);
         x.l("Lbs%s:", K.c_str());
+        x.o += flush_dirty();   // (before EXEC changes: the lanes that ran the trip)
         {   // (inline constants where they fit: VOP3 selects take -16..64)
           auto inl = [](int64_t v) { return v >= -16 && v <= 64; };
           std::string f = std::to_string(fall), t = std::to_string(tgt);
@@ -4606,7 +4960,7 @@ struct RunCompile {
           }
           x.l("v_add_u32_e32 %s, %s, %s", VCNT, VCNT, X0);
         }
-        x.l("s_add_u32 s65, s65, 0x%x", r.cnt);
+        x.l("s_add_u32 s65, s65, 0x%x", r.cnt + pre_cnt);
         flush(x);
         if (fall != tgt && !hybrid && !depth_pick) {   // (hybrid: every split goes to Lsched, hence the trips)
           // No waiting lane at or below the nearer destination `lo`: the lanes going
@@ -4640,12 +4994,12 @@ struct RunCompile {
         extra += x.o;
       } else {
         const std::string lab_split = "Lx" + K + "_" + std::to_string(e.stubs.size());
-        e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone});
+        e.stubs.push_back(Em::Stub{lab_split, e.pc, e.done, e.cdone, e.def_fix()});
         e.l("s_cbranch_scc0 %s", lab_split.c_str());   // lanes disagree: the C++ step splits
       }
     }
     e.gas_add(uint64_t(int64_t(c_fall) + c_adj));
-    e.l("s_add_u32 s65, s65, 0x%x", taken_cnt);
+    e.l("s_add_u32 s65, s65, 0x%x", taken_cnt + pre_cnt);
     fast_to(tgt, true, false);
     e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
     taken_checks();
@@ -4653,13 +5007,16 @@ struct RunCompile {
     if (lop != OP_JMP) {
       e.l("%s:", nt.c_str());
       (void)bcnt;
+      e.o += flush_dirty();   // (the loop is left: once)
       fallthrough(r.cnt);
     }
   }
 
   // the exit to the scheduler, the out-of-line code and the leave stubs
   void finish() {
+    const size_t hot = e.o.size();
     e.l("Lxs%s:", K.c_str());
+    e.o += flush_dirty();
     if (sx & 4) {   // reached a waiting lane or the count limit: merge / reschedule
       long_jump(e, "Lmerge", "Lmq" + K);
     } else {
@@ -4671,10 +5028,18 @@ struct RunCompile {
     e.o += e.tail;
     for (const auto &s : e.stubs) {   // leave before instruction s.pc
       e.l("%s:", s.lab.c_str());
+      e.o += s.fix;
+      e.o += flush_dirty();
       e.gas_add(s.cdone);
       e.l("s_mov_b32 s62, 0x%x", s.pc * 32u);
-      e.l("s_add_u32 s65, s65, 0x%x", s.done);
+      e.l("s_add_u32 s65, s65, 0x%x", s.done + pre_cnt);
       e.l("s_setpc_b64 s[70:71]");
+    }
+    if (tight && var == 1) {   // (placed after p's code: jit_source)
+      cold = callee_cold + e.o.substr(hot);
+      e.o.resize(hot);
+    } else {
+      e.o.insert(hot, callee_cold);
     }
   }
 
@@ -4736,10 +5101,13 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
   const bool depth_pick = simt && kn.depth && recursive(P);
   if (simt) body += simt_sched(t, hybrid, depth_pick);
   const SimtCtx ctx{t, kn, ix, runs, pl, nob, sx, hybrid, depth_pick};
+  std::string cold;   // a copy c's out-of-line code: after the p copy it falls through into
   for (const auto &job : pl.jobs) {
     RunCompile rc(ctx, job.first, job.second);
     if (!rc.compile()) return "";   // jit_runs only picks compilable instructions
     body += rc.e.o;
+    if (job.second != 1) body += cold;
+    cold = job.second == 1 ? rc.cold : std::string();
   }
   if (hybrid) body += trip_source(t, kn, ix, runs, true);
   body = resolve_jumps(body);

@@ -31,6 +31,9 @@ struct JitKnobs {
   bool fwd;            // WB_FWD=0: no loop-carried forwarding copies
   bool fwd_store;      // WB_FWD_STORE=0: a forwarded word is copied after its store
   bool fwd_alias;      // WB_FWD_ALIAS=0: a forwarded load is a move, not a renamed cell
+  bool kprop;          // WB_KPROP=0: every CONST32 / MOV32 of a compiled run writes its register
+  bool fwd_lazy;       // WB_FWD_LAZY=0: a forwarding copy's stores go to memory every trip
+  bool fwd_loop;       // WB_FWD_LOOP=0: the copies keep their stack check, jump and second count
   bool ret_pf;         // WB_RET_PF=0: POST_CALL never reads the RET's record along
   bool brt_thread;     // WB_BRT_THREAD=0: a JMP onto a br_table's run does not take the table
   bool trip_fwd;       // WB_TRIP_FWD=0: no trip-mode load cache
