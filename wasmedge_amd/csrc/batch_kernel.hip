@@ -195,7 +195,8 @@ struct HbmFrame {
 // retired (v93): in SIMT mode (KParams::simt) the compiled runs schedule the lanes among
 // themselves (jit.cpp Lsched), otherwise ALL = the group = EXEC throughout. The caller's
 // EXEC (`ex`) is restored at the end. s[98:99] = the wave's block of the memories past the
-// first (KParams::xmem; the compiled XLD / XST, jit.cpp emit_xmem), 0 without them.
+// first (KParams::xmem; the compiled XLD / XST, jit.cpp emit_xmem), 0 without them. s100 is
+// the compiled runs' alone (jit.cpp TRIPS: a forwarding loop's count-down).
 #define TC_RUN_VF_ASM(...) \
   asm volatile( \
       "s_mov_b32 s60, %[clo]\n\t" \
@@ -260,7 +261,7 @@ struct HbmFrame {
       : "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69", "s70", "s71", \
         "s72", "s73", "s74", "s75", "s76", "s77", "s78", "s79", "s80", "s81", "s82", "s83", \
         "s84", "s85", "s86", "s87", "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96", "s97", \
-        "s98", "s99", \
+        "s98", "s99", "s100", \
         "v92", "v93", "v94", "v98", "v95", "v96", "v97", "v99", "v100", "v101", "v102", "v103", "v104", "v105", "v106", "v107", "v108", "v109", "v110", "v111", "v112", "v113", \
         "v114", "v115", "v116", "v117", "v118", "v119", "v120", "v121", "v122", "v123", \
         "v124", "v125", "v126", "v127", "vcc", "scc", "memory", ##__VA_ARGS__);

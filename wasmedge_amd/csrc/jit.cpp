@@ -38,6 +38,8 @@ const char *const X0 = "v118", *const X1 = "v119", *const XP = "v[118:119]";
 const char *const Y0 = "v120", *const Y1 = "v121";
 const char *const Z0 = "v126", *const Z1 = "v127", *const ZP = "v[126:127]";
 const char *const T2 = "s[74:75]";
+// a tight forwarding loop's count-down (RunCompile::hoist); nothing else names it
+const char *const TRIPS = "s100";
 
 uint16_t op_of(const DInstr &I) { return uint16_t(I.w0 & 0x7FFFu); }
 
@@ -4084,6 +4086,7 @@ JitKnobs jit::read_knobs() {
   k.kprop = on("WB_KPROP");
   k.fwd_lazy = on("WB_FWD_LAZY");
   k.fwd_loop = on("WB_FWD_LOOP");
+  k.fwd_tail = k.fwd_loop && on("WB_FWD_TAIL");
   k.ret_pf = on("WB_RET_PF");
   k.brt_thread = on("WB_BRT_THREAD");
   k.trip_fwd = on("WB_TRIP_FWD");
@@ -4260,6 +4263,13 @@ struct RunCompile {
       lazy = kn.fwd_lazy && kn.fwd_store && var != 0 && !loop->dirty.empty();
       tight = kn.fwd_loop;
       if (tight && var == 2) pre_cnt = runs[R].cnt + runs[size_t(pl.inl_f[R])].cnt;
+      const JitRun &rp = runs[loop->post];
+      const DInstr &br = P.code[rp.pc + rp.len - 1];   // (fwd_plan: a branch to R's start)
+      if (tight && kn.fwd_tail && op_of(br) != OP_JMP) {
+        hoist = true;
+        trip_cnt = uint32_t(int32_t(rp.cnt) + int32_t(int16_t(br.w2 >> 16))) + runs[R].cnt +
+                   runs[size_t(pl.inl_f[R])].cnt;
+      }
     }
   }
 
@@ -4269,10 +4279,29 @@ struct RunCompile {
   // the POST_CALL (p has no other entry: its head is not emitted, c's out-of-line code
   // follows p's: `cold`), and R and c leave the inlined call's count to p's ways out
   // (pre_cnt), which add it with their own.
+  // hoist (a tight loop whose back edge is conditional): LOW, OTHER and the count limit
+  // do not change while the group stays in the c / p pair, so p's full tail runs only on
+  // the trip out of R and when the count-down below runs out. When it lets the group go
+  // on, its head Lhd sets TRIPS (s100) to a number of further trips that surely stay
+  // under the limit (a multiply by 2^32 / trip_cnt rounded down: at most one trip short)
+  // and adds all of them to CNT at once; a trip then ends in the compare of VCC with EXEC
+  // (every lane took the branch) and the count-down. Every other way out of the pair
+  // first takes the trips not run off CNT again (cnt_fix) and clears TRIPS; R clears it
+  // before it enters p, so the fix is a no-op on the trip out of R.
   const FwdPlan *loop = nullptr;
-  bool lazy = false, tight = false;
-  uint32_t pre_cnt = 0;
+  bool lazy = false, tight = false, hoist = false;
+  uint32_t pre_cnt = 0, trip_cnt = 0;
   std::string cold, callee_cold;   // (callee_cold: an inlined callee's out-of-line code)
+
+  // CNT = entry CNT + the trips run (s68 and SCC change)
+  std::string cnt_fix() const {
+    if (!hoist || var == 0) return "";
+    Em d(t);
+    d.l("s_mul_i32 s68, %s, 0x%x", TRIPS, trip_cnt);
+    d.l("s_sub_u32 s65, s65, s68");
+    d.l("s_mov_b32 %s, 0", TRIPS);
+    return d.o;
+  }
 
   // The dirty words (F registers) to memory, under the current exec (the lanes that ran
   // the trip): vector code only -- no scalar register, SCC or VCC changes. R raised the
@@ -4490,12 +4519,13 @@ struct RunCompile {
   // OTHER -- the jump goes straight there; else the full checks below (go, taken_checks)
   // run as before. `lim`: the limit is already in s68 (budget ? OTHER : 0) -- a return's
   // shared prefix, see below.
-  void fast_to(uint32_t to, bool taken, bool lim) {
+  // `via`: the label to jump to instead of the run's (a hoisted loop's head)
+  void fast_to(uint32_t to, bool taken, bool lim, const std::string &via = std::string()) {
     auto it = ix.start.find(to);
     if (it == ix.start.end()) return;
     const uint32_t tend = (to + runs[it->second].len - 1) * 32u;
-    const std::string tl = "Lb" + std::to_string(it->second) +
-                           copy_sfx(it->second);
+    const std::string tl = !via.empty() ? via : "Lb" + std::to_string(it->second) +
+                                                    copy_sfx(it->second);
     if (lim) {
       e.l("s_cmp_gt_u32 s68, 0x%x", tend);
     } else if (taken) {
@@ -4740,7 +4770,9 @@ struct RunCompile {
         ei.l("s_load_dwordx8 s[84:91], s[60:61], s68 offset:0x20");
       }
     }
-    ei.l("s_mov_b32 s62, 0x%x", (callpc + 1) * 32u);
+    // (hoist: p's tail is a branch's, which sets PCOFF on every way that reads it)
+    if (!(hoist && fwd && var == 1)) ei.l("s_mov_b32 s62, 0x%x", (callpc + 1) * 32u);
+    if (hoist && fwd && var == 0) ei.l("s_mov_b32 %s, 0", TRIPS);
     if (!(tight && var == 1))   // (c falls through into p's code)
       long_jump(ei, "Lpa" + std::to_string(inl_post) + (fwd ? "p" : ""), "Lpq" + IK);
     // leaves inside the callee: make the call real first
@@ -4762,7 +4794,7 @@ struct RunCompile {
     e.o += ei.o;
     ei.o = ei.tail;
     for (const auto &st : ei.stubs) {   // (deferred cells and dirty words first)
-      ei.o += st.lab + ":\n" + st.fix + flush_dirty() + deopt;
+      ei.o += st.lab + ":\n" + st.fix + flush_dirty() + deopt + cnt_fix();
       ei.l("s_mov_b32 s62, 0x%x", st.pc * 32u);
       ei.l("s_add_u32 s65, s65, 0x%x", st.done);
       ei.l("s_setpc_b64 s[70:71]");
@@ -4925,6 +4957,9 @@ struct RunCompile {
     const int32_t tcnt = int32_t(int16_t(last.w2 >> 16));
     const uint32_t taken_cnt = uint32_t(int32_t(r.cnt) + tcnt);   // (cnt + tcnt >= 0)
     const std::string nt = "Lnt" + K;
+    // (a tight loop's p copy: the back edge enters the c copy)
+    const bool hoisted = hoist && var == 2 && lop != OP_JMP && ix.has(tgt);
+    const std::string head = hoisted ? "Lb" + std::to_string(ix.at(tgt)) + copy_sfx(ix.at(tgt)) : "";
     if (lop != OP_JMP) {
       if (cmp_any) {   // VCC = the lanes whose any_true is 1
         if (lop == OP_BR_UNLESS) e.l("s_not_b64 vcc, vcc");
@@ -4935,6 +4970,27 @@ struct RunCompile {
         }
         branch_cond(e, last);
         e.alias_cell = -1;
+      }
+      if (hoisted) {
+        // the trip's end: every lane of the group goes round again (VCC names no other
+        // lane) and a trip is left of those Lhd counted; else the full tail below
+        e.l("s_cmp_eq_u64 vcc, exec");
+        e.l("s_cbranch_scc0 Lsl%s", K.c_str());
+        e.l("s_add_u32 %s, %s, -1", TRIPS, TRIPS);   // (SCC: it was not 0)
+        cond_jump(e, head, "Lft" + K);
+        e.l("s_mov_b32 %s, 0", TRIPS);
+        e.l("Lsl%s:", K.c_str());
+        e.o += cnt_fix();
+        Em x(t);
+        x.l("Lhd%s:", K.c_str());   // CNT < LIM here: (LIM - CNT - 1) / trip_cnt further trips
+        x.l("s_sub_u32 s68, s64, s65");
+        x.l("s_sub_u32 s68, s68, 1");
+        x.l("s_mul_hi_u32 %s, s68, 0x%x", TRIPS,
+            uint32_t(std::min<uint64_t>(0xFFFFFFFFull, (1ull << 32) / trip_cnt)));
+        x.l("s_mul_i32 s68, %s, 0x%x", TRIPS, trip_cnt);
+        x.l("s_add_u32 s65, s65, s68");
+        long_jump(x, head, "Lhq" + K);
+        extra += x.o;
       }
       e.l("s_and_b64 %s, vcc, exec", T2);
       e.l("s_cbranch_scc0 %s", nt.c_str());    // no lane takes it
@@ -5000,7 +5056,7 @@ struct RunCompile {
     }
     e.gas_add(uint64_t(int64_t(c_fall) + c_adj));
     e.l("s_add_u32 s65, s65, 0x%x", taken_cnt + pre_cnt);
-    fast_to(tgt, true, false);
+    fast_to(tgt, true, false, hoisted ? "Lhd" + K : std::string());
     e.l("s_mov_b32 s62, 0x%x", tgt * 32u);
     taken_checks();
     go(tgt, false);
@@ -5017,6 +5073,7 @@ struct RunCompile {
     const size_t hot = e.o.size();
     e.l("Lxs%s:", K.c_str());
     e.o += flush_dirty();
+    e.o += cnt_fix();
     if (sx & 4) {   // reached a waiting lane or the count limit: merge / reschedule
       long_jump(e, "Lmerge", "Lmq" + K);
     } else {
@@ -5030,6 +5087,7 @@ struct RunCompile {
       e.l("%s:", s.lab.c_str());
       e.o += s.fix;
       e.o += flush_dirty();
+      e.o += cnt_fix();
       e.gas_add(s.cdone);
       e.l("s_mov_b32 s62, 0x%x", s.pc * 32u);
       e.l("s_add_u32 s65, s65, 0x%x", s.done + pre_cnt);

@@ -34,6 +34,7 @@ struct JitKnobs {
   bool kprop;          // WB_KPROP=0: every CONST32 / MOV32 of a compiled run writes its register
   bool fwd_lazy;       // WB_FWD_LAZY=0: a forwarding copy's stores go to memory every trip
   bool fwd_loop;       // WB_FWD_LOOP=0: the copies keep their stack check, jump and second count
+  bool fwd_tail;       // WB_FWD_TAIL=0: a tight loop tests LOW, OTHER and the count limit every trip
   bool ret_pf;         // WB_RET_PF=0: POST_CALL never reads the RET's record along
   bool brt_thread;     // WB_BRT_THREAD=0: a JMP onto a br_table's run does not take the table
   bool trip_fwd;       // WB_TRIP_FWD=0: no trip-mode load cache
