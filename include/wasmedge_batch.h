@@ -540,6 +540,48 @@ WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets,
                                  uint32_t Offset, const uint32_t *Lens, uint32_t Len, uint8_t *Dst,
                                  uint64_t Stride, uint8_t *PerInstance);
+/* Instance snapshots: the state of EVERY instance as it stands between runs, held on the
+ * device, and a restore that starts instance i from the captured state of instance SrcOf[i]
+ * (SrcOf NULL: from its own) -- rewind after each try, fork, broadcast, survivor selection.
+ * The reference has no counterpart (one VM is one instance; it would instantiate N VMs and
+ * run their setup again). A restored instance continues exactly as its source would have.
+ *
+ * Captured and restored: memory 0 (contents, size and write mark of every instance),
+ * memories 1..7 and their sizes, the globals, the per-instance tables with their sizes and
+ * dropped element segments, the dropped data segments, the instantiation status, the gas
+ * total (WasmEdge_BatchGetTotalCosts) and the built-in WASI state of every instance (captured
+ * stdout / stderr, exit code, fd table, generator and clock counters; mapped through SrcOf,
+ * except that an instance keeps its own index and its own args).
+ * Not captured: frames and the call stack (a snapshot is taken between runs, when no
+ * instance is parked at a host function), staged arguments and calls, the last run's results
+ * (after a restore WasmEdge_BatchResults fails as after a BatchReset, until the next run),
+ * externref handles (they live as long as the context) and the memory layout, which a
+ * restore neither changes nor depends on: a snapshot stays valid when the granule, the
+ * reserved pages or the table capacities changed since. The start function does not run
+ * again.
+ *
+ * SnapshotCreate returns NULL and sets *Res on failure: WrongVMWorkflow (0x04) for a NULL
+ * context; RuntimeError (0x02) with a WasmEdge_BatchGetLastError message when device memory
+ * runs out, or when instances hold pages past the reserved layout and it cannot grow to take
+ * them (the context stays usable). GetBytes: the device memory the snapshot holds, in bytes
+ * -- what the instances wrote, not the size of their memories.
+ *
+ * SnapshotRestore fails, with all state unchanged, with WrongVMWorkflow (0x04) for a NULL
+ * context or snapshot, a snapshot of another context (or of one deleted since) or some
+ * SrcOf[i] >= NumInstances, and with RuntimeError (0x02) and a message for a non-NULL SrcOf on
+ * a multi-device context (rows cannot cross devices; NULL works there). *KernelSeconds (may
+ * be NULL) = the device time of the restore; NULL: no host synchronisation, the next launch
+ * orders after it, as with BatchReset. A snapshot outlives BatchReset and other restores and
+ * may be restored any number of times; SnapshotDelete is safe before or after BatchDelete of
+ * its context. Not to be called from inside a host function. */
+typedef struct WasmEdge_BatchSnapshot WasmEdge_BatchSnapshot;
+WASMEDGE_BATCH_API WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *Cxt,
+                                                                        WasmEdge_Result *Res);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *Cxt, const WasmEdge_BatchSnapshot *Snap,
+                              const uint32_t *SrcOf, double *KernelSeconds);
+WASMEDGE_BATCH_API uint64_t WasmEdge_BatchSnapshotGetBytes(const WasmEdge_BatchSnapshot *Snap);
+WASMEDGE_BATCH_API void WasmEdge_BatchSnapshotDelete(WasmEdge_BatchSnapshot *Snap);
 /* Exported tables and globals of one instance, by export name (the batched form of
  * WasmEdge_StoreFindTable/FindGlobal + WasmEdge_TableInstanceGetData/SetData/GetSize,
  * lib/api/wasmedge.cpp:2099-2139, and WasmEdge_GlobalInstanceGetValue/SetValue,

@@ -221,6 +221,14 @@ def lib():
         L.WasmEdge_BatchGetExtraMemoryPages.argtypes = [vp, u32]
         L.WasmEdge_BatchGetEngine.restype = ctypes.c_char_p
         L.WasmEdge_BatchGetEngine.argtypes = [vp]
+        L.WasmEdge_BatchSnapshotCreate.restype = vp
+        L.WasmEdge_BatchSnapshotCreate.argtypes = [vp, ctypes.POINTER(_Result)]
+        L.WasmEdge_BatchSnapshotRestore.restype = _Result
+        L.WasmEdge_BatchSnapshotRestore.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double)]
+        L.WasmEdge_BatchSnapshotGetBytes.restype = u64
+        L.WasmEdge_BatchSnapshotGetBytes.argtypes = [vp]
+        L.WasmEdge_BatchSnapshotDelete.restype = None
+        L.WasmEdge_BatchSnapshotDelete.argtypes = [vp]
         _lib = L
     return _lib
 
@@ -418,6 +426,31 @@ class BatchContext:
         ints = ret_ints(rets)
         out = [[int(x) for x in ints[i][:lens[i]]] if status[i] == 0 else [] for i in range(self.n)]
         return out, status, counts
+
+    # instance snapshots (WasmEdge_BatchSnapshotCreate / Restore)
+    def snapshot(self):
+        """Capture every instance's state as it stands between runs; returns a Snapshot."""
+        res = _Result(0)
+        h = lib().WasmEdge_BatchSnapshotCreate(self._h, ctypes.byref(res))
+        if not h:
+            raise WasmEdgeError(res.Code, lib().WasmEdge_BatchGetLastError(self._h).decode())
+        return Snapshot(h)
+
+    def restore(self, snap, src_of=None, timed=True):
+        """Instance i restarts from the captured state of instance src_of[i] (None: its own);
+        returns the restore kernels' time (timed=False: no host synchronisation, returns 0)."""
+        if not isinstance(snap, Snapshot) or not snap._h:
+            raise ValueError("a Snapshot that is not closed is needed")
+        src = None
+        if src_of is not None:
+            src = np.ascontiguousarray(src_of, np.uint32)
+            if src.shape != (self.n,):
+                raise ValueError("src_of must have %d entries" % self.n)
+        t = ctypes.c_double(0)
+        self._check(lib().WasmEdge_BatchSnapshotRestore(self._h, snap._h,
+                                                        src.ctypes.data if src is not None else None,
+                                                        ctypes.byref(t) if timed else None))
+        return t.value
 
     def total_costs(self):
         """Each instance's gas total (WasmEdge_BatchGetTotalCosts)."""
@@ -631,6 +664,28 @@ class BatchContext:
         buf = ctypes.create_string_buffer(max(n, 1))
         lib().WasmEdge_BatchWASIGetOutput(self._h, inst, fd, buf, n)
         return buf.raw[:n]
+
+
+class Snapshot:
+    """The captured state of a BatchContext's instances (WasmEdge_BatchSnapshot), held on the
+    device until close(). It belongs to the context it was taken from and may be closed
+    before or after it."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @property
+    def nbytes(self):
+        """Device bytes the snapshot holds."""
+        return int(lib().WasmEdge_BatchSnapshotGetBytes(self._h)) if self._h else 0
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().WasmEdge_BatchSnapshotDelete(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
 
 
 def _cstrs(v):

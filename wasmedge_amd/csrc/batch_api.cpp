@@ -1467,6 +1467,7 @@ void WasmEdge_BatchInterrupt(WasmEdge_BatchContext *C) {
 
 void WasmEdge_BatchDelete(WasmEdge_BatchContext *C) {
   if (!C) return;
+  wbs::orphan(C);
   if (!C->shards.empty()) {
     wbm::destroy(C);
     return;

@@ -56,6 +56,9 @@ struct DevBuf {
 }  // namespace wbh
 
 namespace wbh { struct WaveView; }
+struct WasmEdge_BatchSnapshot;
+// snapshot.cpp: the context goes, its snapshots stay behind inert
+namespace wbs { void orphan(WasmEdge_BatchContext *C); }
 
 // a Reset left to the next launch (batch_kernel.hip fused_reset) done now, as its own
 // kernel: for a host accessor or any device work that reads instance state first
@@ -225,6 +228,8 @@ struct WasmEdge_BatchContext {
   bool reset_pending = false;
   // ... or not even queued: the next launch of the interpreter does it (fused_reset)
   bool reset_deferred = false;
+  // the snapshots taken from this context and not yet deleted (snapshot.cpp)
+  std::vector<WasmEdge_BatchSnapshot *> snaps;
 
   // Multi-device contexts (WasmEdge_BatchConfigure::Devices, multi.cpp): the parent holds
   // one shard context per entry of Devices (nullptr: no instances there) and routes every

@@ -1,0 +1,363 @@
+// snapshot.cpp -- instance snapshots (WasmEdge_BatchSnapshotCreate / Restore / GetBytes /
+// Delete; DESIGN.md "Instance snapshots"): the state of every instance as it stands between
+// runs, held on the device, and a restore that starts instance i from the captured state of
+// instance SrcOf[i]. The device side is snapshot.hip; the planning that needs no device is
+// snapshot_plan.h.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <mutex>
+#include <vector>
+
+#include "batch_ctx.h"
+#include "multi.h"
+#include "snapshot.h"
+#include "snapshot_plan.h"
+
+extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s);
+extern "C" hipError_t wb_launch_snap_rows(const SnapRowsParams *p, hipStream_t s);
+
+using namespace wbh;
+using Ctx = WasmEdge_BatchContext;
+
+struct WasmEdge_BatchSnapshot {
+  Ctx *ctx = nullptr;   // the context it was taken from; NULL once that was deleted (inert)
+  int device = 0;
+  std::vector<WasmEdge_BatchSnapshot *> subs;   // a multi-device context's: one per shard
+  // the layout it was taken under (a restore translates to the context's current one)
+  uint32_t n = 0, nwaves = 0, mlog = 0, mem_words = 0, ls_slots = 0, tab_words = 0, xlog = 0, xwords = 0;
+  std::vector<uint32_t> tabinfo;
+  // memory 0: rows [0, rows_h[w]) of wave w at word off[w] of `mem` (snapshot_plan.h pack_rows)
+  std::vector<uint32_t> rows_h;
+  uint32_t max_tiles = 0;
+  DevBuf<uint32_t> mem, rows;
+  DevBuf<uint64_t> off;
+  DevBuf<uint32_t> lstate, ltab, xmem, xpages;   // copied whole
+  std::vector<wbw::Lane> wasi;
+  uint64_t bytes = 0;
+  // the last restore's plan and its device copy (kept here so that an untimed restore leaves
+  // nothing of its own to free while its kernels run)
+  mutable wbs::RestorePlan plan;
+  mutable DevBuf<uint32_t> plan_src, plan_wave;
+};
+using Snap = WasmEdge_BatchSnapshot;
+
+namespace wbs {
+
+static std::mutex g_mu;   // the contexts' lists of their snapshots
+
+void orphan(Ctx *C) {
+  std::lock_guard<std::mutex> g(g_mu);
+  for (Snap *s : C->snaps) s->ctx = nullptr;
+  C->snaps.clear();
+}
+
+}  // namespace wbs
+
+namespace {
+
+// blocks per wave for the memory kernels: enough blocks to fill the device when the batch
+// has few waves, no more than the tiles there are
+uint32_t chunks_for(uint32_t nwaves, uint32_t max_tiles) {
+  const uint32_t cap = std::max<uint32_t>(8, 4096 / std::max<uint32_t>(nwaves, 1));
+  return std::min(std::max<uint32_t>(max_tiles, 1), cap);
+}
+
+// one LS slot of every lane, [nwaves][64], with one strided copy (as Reset fetches the pages)
+bool fetch_slot(Ctx *C, uint32_t slot, std::vector<uint32_t> *out) {
+  const size_t row = 64 * sizeof(uint32_t), pitch = size_t(C->ls_slots) * row;
+  out->assign(size_t(C->nwaves) * 64, 0);
+  return C->hip_ok(hipMemcpy2D(out->data(), row, C->lstate.ptr + size_t(slot) * 64, pitch, row, C->nwaves,
+                               hipMemcpyDeviceToHost), "instance state");
+}
+
+template <typename T>
+bool copy_whole(Ctx *C, DevBuf<T> *to, const DevBuf<T> &from, size_t count, uint64_t *bytes) {
+  if (!count) return true;
+  if (!to->alloc(count)) {
+    (void)hipGetLastError();
+    C->last_error = "snapshot: no device memory";
+    return false;
+  }
+  *bytes += count * sizeof(T);
+  return C->hip_ok(hipMemcpyAsync(to->ptr, from.ptr, count * sizeof(T), hipMemcpyDeviceToDevice, C->stream),
+                   "snapshot");
+}
+
+Snap *create_one(Ctx *C, uint8_t *code) {
+  DevScope dev(C);
+  const wb::Program &P = C->prog;
+  *code = kRuntimeError;
+  // a Reset that did not wait, or was left to the next launch, is carried out first: the
+  // capture must see the reset state
+  if (!C->settle() || !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot")) return nullptr;
+  // instances that hold pool rows: the reserved layout takes them (hostcall.cpp grow_layout),
+  // so that a snapshot never holds a page at or above the rpages it records
+  if (C->grow_host && C->pool_used) {
+    std::vector<uint32_t> pages;
+    if (!fetch_slot(C, LS_PAGES, &pages)) return nullptr;
+    uint32_t reached = 0;
+    for (uint32_t i = 0; i < C->n; i++) reached = std::max(reached, pages[i]);
+    if (reached > C->rpages && !grow_layout(C, reached, reached, true)) return nullptr;
+    if (reached > C->rpages) {
+      C->last_error = "snapshot: instances hold pages past the reserved layout, which cannot grow to take "
+                      "them (device memory, MemoryPoolBytes or WB_RELAYOUT=0)";
+      return nullptr;
+    }
+  }
+  std::unique_ptr<Snap> S(new Snap());
+  S->device = C->device;
+  S->n = C->n;
+  S->nwaves = C->nwaves;
+  S->mlog = C->mlog;
+  S->mem_words = C->mem_words;
+  S->ls_slots = C->ls_slots;
+  S->tab_words = P.mut_tables ? P.tab_words : 0;
+  S->tabinfo = P.tabinfo;
+  S->xlog = C->xlog;
+  S->xwords = C->xwords;
+  // memory 0: the rows below every wave's write-mark bound, packed
+  std::vector<uint32_t> marks;
+  std::vector<uint64_t> off;
+  if (!fetch_slot(C, LS_HWM, &marks)) return nullptr;
+  const uint32_t mw = P.has_mem ? C->mem_words : 0;
+  const uint64_t words = wbs::pack_rows(marks.data(), C->nwaves, C->image_words, mw, &S->rows_h, &off);
+  for (uint32_t r : S->rows_h) S->max_tiles = std::max(S->max_tiles, r / wbs::kTile);
+  if (!S->mem.alloc(size_t(words) + 4) || !S->rows.upload(S->rows_h, C->stream) || !S->off.upload(off, C->stream)) {
+    (void)hipGetLastError();
+    C->last_error = "snapshot: no device memory";
+    return nullptr;
+  }
+  S->bytes = (words + 4) * 4 + uint64_t(C->nwaves) * 12;
+  SnapMemParams p{};
+  p.mem = C->mem.ptr;
+  p.snap = S->mem.ptr;
+  p.snap_off = S->off.ptr;
+  p.snap_rows = S->rows.ptr;
+  p.nwaves = C->nwaves;
+  p.mem_words = mw;
+  p.ls_slots = C->ls_slots;
+  p.image_words = C->image_words;
+  p.g_mem = p.g_snap = C->mlog;
+  p.chunks = chunks_for(C->nwaves, S->max_tiles);
+  if (words && !C->hip_ok(wb_launch_snap_mem(&p, 0, C->stream), "snapshot")) return nullptr;
+  // instance state, per-lane tables, memories 1..7 and their sizes: whole
+  const size_t nw = C->nwaves;
+  if (!copy_whole(C, &S->lstate, C->lstate, nw * C->ls_slots * 64, &S->bytes) ||
+      !copy_whole(C, &S->ltab, C->ltab, nw * S->tab_words * 64, &S->bytes) ||
+      !copy_whole(C, &S->xmem, C->xmem, P.xmems.empty() ? 0 : nw * 64 * size_t(C->xwords), &S->bytes) ||
+      !copy_whole(C, &S->xpages, C->xpages, P.xmems.empty() ? 0 : C->xpages0.size(), &S->bytes) ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot"))
+    return nullptr;
+  S->wasi = C->wasi_lanes;
+  S->ctx = C;
+  {
+    std::lock_guard<std::mutex> g(wbs::g_mu);
+    C->snaps.push_back(S.get());
+  }
+  *code = 0;
+  return S.release();
+}
+
+void delete_one(Snap *S) {
+  {
+    std::lock_guard<std::mutex> g(wbs::g_mu);
+    if (S->ctx) {
+      auto &v = S->ctx->snaps;
+      v.erase(std::remove(v.begin(), v.end(), S), v.end());
+    }
+  }
+  for (Snap *s : S->subs)
+    if (s) delete_one(s);
+  int cur = -1;
+  const bool sw = !S->subs.size() && hipGetDevice(&cur) == hipSuccess && cur != S->device &&
+                  hipSetDevice(S->device) == hipSuccess;
+  delete S;   // (its device buffers)
+  if (sw) (void)hipSetDevice(cur);
+}
+
+uint8_t rows_launch(Ctx *C, uint32_t *dst, const uint32_t *src, const uint32_t *src_of, uint32_t words_d,
+                    uint32_t words_s, uint32_t base_d, uint32_t base_s, uint32_t count, uint32_t g,
+                    uint32_t fill, uint32_t ls_fix) {
+  SnapRowsParams r{};
+  r.dst = dst;
+  r.src = src;
+  r.src_of = src_of;
+  r.nwaves = C->nwaves;
+  r.words_d = words_d;
+  r.words_s = words_s;
+  r.base_d = base_d;
+  r.base_s = base_s;
+  r.count = count;
+  r.g = g;
+  r.fill = fill;
+  r.ls_fix = ls_fix;
+  return C->hip_ok(wb_launch_snap_rows(&r, C->stream), "restore") ? 0 : kRuntimeError;
+}
+
+uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *KernelSeconds) {
+  const wb::Program &P = C->prog;
+  if (SrcOf)
+    for (uint32_t i = 0; i < C->n; i++)
+      if (SrcOf[i] >= C->n) return C->fail(kWrongVMWorkflow, "restore: SrcOf names an instance past NumInstances");
+  // the layout now against the one recorded: the reserved layout and the tables only grow
+  const uint32_t mw = P.has_mem ? C->mem_words : 0;
+  bool fits = S->n == C->n && S->ls_slots == C->ls_slots && S->xwords == C->xwords && S->xlog == C->xlog &&
+              S->tabinfo.size() == P.tabinfo.size() && (!P.has_mem || S->mem_words <= C->mem_words) && !C->mem_fresh;
+  for (size_t t = 0; fits && S->tab_words && 2 * t + 1 < S->tabinfo.size(); t++)
+    fits = S->tabinfo[2 * t + 1] <= P.tabinfo[2 * t + 1];
+  if (!fits) return C->fail(kRuntimeError, "restore: the context's layout cannot hold the snapshot");
+  DevScope dev(C);
+  // A Reset left to the next launch is cancelled, not carried out: the restore re-initialises
+  // every row below the waves' current bound itself and writes every state slot, and that
+  // launch would otherwise wipe what it restored. A Reset that is queued orders before the
+  // restore's kernels on the stream; nothing here reads instance state from the host, so an
+  // untimed restore does not wait for it.
+  C->reset_deferred = false;
+  const bool same = S->mlog == C->mlog;
+  const bool planned = SrcOf || !same;
+  if (planned) {
+    wbs::plan_restore(SrcOf, C->n, C->nwaves, S->rows_h.data(), same, &S->plan);
+    if ((!S->plan_src.ptr && !S->plan_src.alloc(S->plan.src.size())) ||
+        (!S->plan_wave.ptr && !S->plan_wave.alloc(S->plan.wave.size()))) {
+      (void)hipGetLastError();
+      return C->fail(kRuntimeError, "restore: no device memory");
+    }
+    if (!C->hip_ok(hipMemcpyAsync(S->plan_src.ptr, S->plan.src.data(), S->plan.src.size() * 4,
+                                  hipMemcpyHostToDevice, C->stream), "restore") ||
+        !C->hip_ok(hipMemcpyAsync(S->plan_wave.ptr, S->plan.wave.data(), S->plan.wave.size() * 4,
+                                  hipMemcpyHostToDevice, C->stream), "restore"))
+      return kRuntimeError;
+  }
+  const uint32_t *src_of = SrcOf ? S->plan_src.ptr : nullptr;
+  (void)hipEventRecord(C->ev0, C->stream);
+  // no restored lane needs a pool row (create_one): the context's go back
+  if (!pool_reset(C)) return kRuntimeError;
+  SnapMemParams p{};
+  p.mem = C->mem.ptr;
+  p.snap = S->mem.ptr;
+  p.snap_off = S->off.ptr;
+  p.snap_rows = S->rows.ptr;
+  p.lstate = C->lstate.ptr;
+  p.image = C->image.ptr;
+  p.src = S->plan_src.ptr;
+  p.wave_plan = S->plan_wave.ptr;
+  p.nwaves = C->nwaves;
+  p.mem_words = mw;
+  p.ls_slots = C->ls_slots;
+  p.image_words = C->image_words;
+  p.g_mem = C->mlog;
+  p.g_snap = S->mlog;
+  // (the current bounds are the device's to read; the snapshot's rows size the grid)
+  p.chunks = chunks_for(C->nwaves, S->max_tiles);
+  if (!C->hip_ok(wb_launch_snap_mem(&p, planned && !S->plan.identity ? 2 : 1, C->stream), "restore"))
+    return kRuntimeError;
+  // the state slots after memory 0 (whose kernel read the current marks), "not parked"
+  uint8_t e = rows_launch(C, C->lstate.ptr, S->lstate.ptr, src_of, C->ls_slots, S->ls_slots, 0, 0, C->ls_slots, 0, 0, 1);
+  // per-lane tables, table by table: the capacities may have widened since (widen_tables);
+  // the slots past the captured capacity are null
+  for (uint32_t t = 0; !e && S->tab_words && t < P.ntables; t++) {
+    const uint32_t fs = S->tabinfo[2 * t], cs = S->tabinfo[2 * t + 1], fc = P.tabinfo[2 * t], cc = P.tabinfo[2 * t + 1];
+    e = rows_launch(C, C->ltab.ptr, S->ltab.ptr, src_of, P.tab_words, S->tab_words, fc, fs, cs, 0, 0, 0);
+    if (!e && cc > cs)
+      e = rows_launch(C, C->ltab.ptr, nullptr, nullptr, P.tab_words, 0, fc + cs, 0, cc - cs, 0, 0xFFFFFFFFu, 0);
+  }
+  if (!e && !P.xmems.empty() && C->xwords)
+    e = rows_launch(C, C->xmem.ptr, S->xmem.ptr, src_of, C->xwords, S->xwords, 0, 0, C->xwords, C->xlog, 0, 0);
+  const size_t xs = size_t(C->nwaves) * 64;
+  for (size_t k = 0; !e && k < P.xmems.size(); k++)
+    e = rows_launch(C, C->xpages.ptr + k * xs, S->xpages.ptr + k * xs, src_of, 1, 1, 0, 0, 1, 0, 0, 0);
+  if (e) return e;
+  (void)hipEventRecord(C->ev1, C->stream);
+  // the host-side WASI lane state through SrcOf; `index` and an instance's own args stay
+  if (!S->wasi.empty() && S->wasi.size() == C->wasi_lanes.size()) {
+    std::vector<wbw::Lane> lanes(C->n);
+    for (uint32_t i = 0; i < C->n; i++) {
+      lanes[i] = S->wasi[SrcOf ? SrcOf[i] : i];
+      lanes[i].index = C->wasi_lanes[i].index;
+      lanes[i].own_args = C->wasi_lanes[i].own_args;
+      lanes[i].args = C->wasi_lanes[i].args;
+    }
+    C->wasi_lanes.swap(lanes);
+  }
+  C->ran = false;
+  C->reset_pending = true;   // host accessors settle() before touching instance state
+  if (KernelSeconds) {
+    C->reset_pending = false;
+    if (!C->hip_ok(hipStreamSynchronize(C->stream), "restore")) return kRuntimeError;
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, C->ev0, C->ev1);
+    *KernelSeconds = ms * 1e-3;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *C, WasmEdge_Result *Res) {
+  if (!C) {
+    if (Res) *Res = R(kWrongVMWorkflow);
+    return nullptr;
+  }
+  uint8_t code = 0;
+  Snap *S = nullptr;
+  if (C->shards.empty()) {
+    S = create_one(C, &code);
+  } else {   // one sub-snapshot per shard
+    S = new Snap();
+    S->n = C->n;
+    S->subs.assign(C->shards.size(), nullptr);
+    for (size_t g = 0; g < C->shards.size() && !code; g++) {
+      if (!C->shards[g]) continue;
+      S->subs[g] = create_one(C->shards[g], &code);
+      if (code) C->last_error = C->shards[g]->last_error;
+      else S->bytes += S->subs[g]->bytes;
+    }
+    if (code) {
+      delete_one(S);
+      S = nullptr;
+    } else {
+      S->ctx = C;
+      std::lock_guard<std::mutex> g(wbs::g_mu);
+      C->snaps.push_back(S);
+    }
+  }
+  if (Res) *Res = R(code);
+  return S;
+}
+
+WasmEdge_Result WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *C, const WasmEdge_BatchSnapshot *S,
+                                              const uint32_t *SrcOf, double *KernelSeconds) {
+  if (!C || !S) return R(kWrongVMWorkflow);
+  if (S->ctx != C) return R(C->fail(kWrongVMWorkflow, "restore: the snapshot was taken from another context"));
+  if (C->shards.empty()) return R(restore_one(C, S, SrcOf, KernelSeconds));
+  if (SrcOf) {
+    for (uint32_t i = 0; i < C->n; i++)
+      if (SrcOf[i] >= C->n) return R(C->fail(kWrongVMWorkflow, "restore: SrcOf names an instance past NumInstances"));
+    return R(C->fail(kRuntimeError, "restore: SrcOf on a multi-device context (rows cannot cross devices); "
+                                    "pass NULL to restore every instance from itself"));
+  }
+  double secs = 0;
+  for (size_t g = 0; g < C->shards.size(); g++) {
+    if (!C->shards[g]) continue;
+    double t = 0;
+    const uint8_t e = restore_one(C->shards[g], S->subs[g], nullptr, KernelSeconds ? &t : nullptr);
+    if (e) {
+      C->last_error = C->shards[g]->last_error;
+      return R(e);
+    }
+    secs = std::max(secs, t);
+  }
+  if (KernelSeconds) *KernelSeconds = secs;
+  return R(0);
+}
+
+uint64_t WasmEdge_BatchSnapshotGetBytes(const WasmEdge_BatchSnapshot *S) { return S ? S->bytes : 0; }
+
+void WasmEdge_BatchSnapshotDelete(WasmEdge_BatchSnapshot *S) {
+  if (S) delete_one(S);
+}
+
+}  // extern "C"

@@ -1,0 +1,70 @@
+// snapshot.hip -- instance snapshots on the device (WasmEdge_BatchSnapshotCreate / Restore;
+// DESIGN.md "Instance snapshots"). A translation unit of its own, like mem_io.hip: the
+// interpreter kernels' object does not change with it.
+//
+// Memory 0 lives lane-interleaved per wave in granules of 2^g words (mem_layout.h), and only
+// the rows below a wave's write-mark bound can differ from zero (wb_mem_init_kernel's
+// invariant), so a snapshot holds those rows alone, packed wave after wave:
+//   * wb_snap_capture_kernel: the rows of every wave into the packed buffer;
+//   * wb_snap_restore_copy_kernel: every lane from itself under the capture's granule -- a
+//     streaming copy of the held tiles, then the tail up to the wave's current bound
+//     re-initialised from the image / zero;
+//   * wb_snap_restore_gather_kernel: lanes from other lanes (fork) or under another granule,
+//     a tile at a time through LDS;
+//   * wb_snap_rows_kernel: the small whole buffers (instance state, per-lane tables, memories
+//     1..7 and their sizes) through the same source map.
+// The bodies are in snapshot_kernels.inc, which also compiles as host code.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "kparams.h"
+#include "mem_layout.h"
+#include "snapshot.h"
+#include "snapshot_plan.h"
+
+#define WB_SNAP_FN __device__ inline
+#define WB_SNAP_SYNC() __syncthreads()
+
+namespace {
+
+#include "snapshot_kernels.inc"
+
+__global__ void __launch_bounds__(256) wb_snap_capture_kernel(const SnapMemParams p) {
+  snap_capture_body(p, blockIdx.x, threadIdx.x);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_restore_copy_kernel(const SnapMemParams p) {
+  __shared__ uint32_t s_m[64];
+  snap_restore_copy_body(p, blockIdx.x, threadIdx.x, s_m);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_restore_gather_kernel(const SnapMemParams p) {
+  __shared__ uint32_t tile[64 * kSnapPitch];
+  __shared__ uint32_t s_m[64], s_src[64];
+  snap_restore_gather_body(p, blockIdx.x, threadIdx.x, tile, s_m, s_src);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_rows_kernel(const SnapRowsParams p) {
+  snap_rows_body(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
+}
+
+}  // namespace
+
+// kind 0: capture, 1: restore (copy), 2: restore (gather); p->chunks blocks per wave
+extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s) {
+  if (p->nwaves == 0 || p->mem_words == 0 || p->chunks == 0) return hipSuccess;
+  const dim3 grid(p->nwaves * p->chunks), block(256);
+  if (kind == 0) hipLaunchKernelGGL(wb_snap_capture_kernel, grid, block, 0, s, *p);
+  else if (kind == 1) hipLaunchKernelGGL(wb_snap_restore_copy_kernel, grid, block, 0, s, *p);
+  else hipLaunchKernelGGL(wb_snap_restore_gather_kernel, grid, block, 0, s, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t wb_launch_snap_rows(const SnapRowsParams *p, hipStream_t s) {
+  const uint64_t total = (uint64_t)p->nwaves * p->count * 64u;
+  if (total == 0) return hipSuccess;
+  const uint64_t blocks = (total + 1023u) / 1024u;   // (4 words per thread where it is large)
+  hipLaunchKernelGGL(wb_snap_rows_kernel, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, s,
+                     *p);
+  return hipGetLastError();
+}

@@ -1,0 +1,178 @@
+// snapshot_kernels.inc -- the bodies of the instance-snapshot kernels (snapshot.hip wraps each
+// in a __global__ function). Plain loads and stores only. The including file defines
+//   WB_SNAP_FN      the function qualifiers (__device__ inline; host: inline)
+//   WB_SNAP_SYNC()  the block barrier (__syncthreads(); host: a barrier of 256 threads)
+// so that the same text runs as host code, a thread per GPU thread, under a sanitizer.
+// A block has 256 threads; block b serves wave b / chunks and, of that wave's tiles,
+// c = b % chunks, c + chunks, ... A tile is 64 words of the wave's 64 lanes: 16 KiB, one
+// contiguous piece of the wave's region at every granule, moved 16 bytes per thread (a wave's
+// access: 1 KiB contiguous). Element x of a tile's 4096 words under granules of 2^g words is
+// word ((x >> (6 + g)) << g) + (x & (2^g - 1)) of lane (x >> g) & 63 (mem_io.hip).
+
+typedef uint32_t wb_snap_v4 __attribute__((vector_size(16)));
+
+constexpr uint32_t kSnapPitch = wbs::kTile + 1u;   // LDS row pitch, as mem_io.hip's tile
+
+WB_SNAP_FN uint32_t snap_elem_lane(uint32_t x, uint32_t g) { return (x >> g) & 63u; }
+WB_SNAP_FN uint32_t snap_elem_word(uint32_t x, uint32_t g) {
+  return ((x >> (6u + g)) << g) + (x & ((1u << g) - 1u));
+}
+
+// the wave's current bound (rows), from its 64 write marks; s_m: 64 words of LDS
+WB_SNAP_FN uint32_t snap_cur_rows(const SnapMemParams &p, uint32_t wave, uint32_t t, uint32_t *s_m) {
+  if (t < 64) s_m[t] = p.lstate[((size_t)wave * p.ls_slots + LS_HWM) * 64u + t];
+  WB_SNAP_SYNC();
+  uint32_t m = 0;
+  for (uint32_t l = 0; l < 64; l++) m = s_m[l] > m ? s_m[l] : m;
+  return wbs::rows_of_mark(m, p.image_words, p.mem_words);   // (clamped to mem_words)
+}
+
+// tile ti of the wave at `to`: the module image, zero past it
+WB_SNAP_FN void snap_init_tile(const SnapMemParams &p, uint32_t *to, uint32_t ti, uint32_t t) {
+  for (uint32_t k = 0; k < 4; k++) {
+    const uint32_t x = 4u * (t + 256u * k);
+    wb_snap_v4 v;
+    for (uint32_t q = 0; q < 4; q++) {
+      const uint32_t w = ti * wbs::kTile + snap_elem_word(x + q, p.g_mem);
+      v[q] = w < p.image_words ? p.image[w] : 0u;
+    }
+    *(wb_snap_v4 *)(to + x) = v;
+  }
+}
+
+// ---- capture: rows [0, snap_rows[wave]) of the layout -> the packed buffer ------------------
+WB_SNAP_FN void snap_capture_body(const SnapMemParams &p, uint32_t b, uint32_t t) {
+  const uint32_t wave = b / p.chunks, c = b % p.chunks;
+  if (wave >= p.nwaves) return;
+  const uint32_t rows = p.snap_rows[wave] < p.mem_words ? p.snap_rows[wave] : p.mem_words;
+  const wb_snap_v4 *from = (const wb_snap_v4 *)(p.mem + (size_t)wave * p.mem_words * 64u);
+  wb_snap_v4 *to = (wb_snap_v4 *)(p.snap + p.snap_off[wave]);
+  for (uint32_t ti = c; ti < rows / wbs::kTile; ti += p.chunks)
+    for (uint32_t k = 0; k < 4; k++) {
+      const size_t i = (size_t)ti * 1024u + t + 256u * k;
+      to[i] = from[i];
+    }
+}
+
+// ---- restore, identity: every lane from itself, under the granule of the capture ----------
+// Tiles below the snapshot's rows are copied as they lie; tiles from there up to the wave's
+// current bound are re-initialised (Reset's work on the tail).
+WB_SNAP_FN void snap_restore_copy_body(const SnapMemParams &p, uint32_t b, uint32_t t, uint32_t *s_m) {
+  const uint32_t wave = b / p.chunks, c = b % p.chunks;
+  if (wave >= p.nwaves) return;
+  const uint32_t cur = snap_cur_rows(p, wave, t, s_m) / wbs::kTile;
+  const uint32_t rows = p.snap_rows[wave] < p.mem_words ? p.snap_rows[wave] : p.mem_words;
+  const uint32_t held = rows / wbs::kTile, ntiles = held > cur ? held : cur;
+  uint32_t *wm = p.mem + (size_t)wave * p.mem_words * 64u;
+  const wb_snap_v4 *from = (const wb_snap_v4 *)(p.snap + p.snap_off[wave]);
+  for (uint32_t ti = c; ti < ntiles; ti += p.chunks) {
+    if (ti >= held) {
+      snap_init_tile(p, wm + (size_t)ti * 4096u, ti, t);
+      continue;
+    }
+    wb_snap_v4 *to = (wb_snap_v4 *)wm;
+    for (uint32_t k = 0; k < 4; k++) {
+      const size_t i = (size_t)ti * 1024u + t + 256u * k;
+      to[i] = from[i];
+    }
+  }
+}
+
+// ---- restore, gather: lanes from other lanes, or under another granule ---------------------
+// tile: 64 * kSnapPitch words of LDS; s_m, s_src: 64 words each. The destination side is
+// always written 16 bytes per thread, contiguous. wbs::kOneWave: the one source wave's tile
+// is read contiguously into LDS rows by SOURCE lane and every destination lane reads its
+// source's row. wbs::kGather: 4 threads per destination lane read its source lane's 64 words
+// -- pieces of 4 << g_snap bytes, 16 bytes per load where the granule holds them, single
+// words at the 4-byte granule -- into LDS rows by DESTINATION lane. A lane whose source wave
+// holds no rows of the tile gets the image / zero.
+WB_SNAP_FN void snap_restore_gather_body(const SnapMemParams &p, uint32_t b, uint32_t t, uint32_t *tile,
+                                         uint32_t *s_m, uint32_t *s_src) {
+  const uint32_t wave = b / p.chunks, c = b % p.chunks;
+  if (wave >= p.nwaves) return;
+  const uint32_t cur = snap_cur_rows(p, wave, t, s_m) / wbs::kTile;
+  if (t < 64) {
+    const uint32_t s = p.src[(size_t)wave * 64u + t];
+    s_src[t] = (s >> 6) < p.nwaves ? s : wave * 64u + t;   // (the host's plan: always in range)
+  }
+  WB_SNAP_SYNC();
+  const uint32_t cls = p.wave_plan[2u * wave], cap = p.mem_words / wbs::kTile;
+  const uint32_t held = p.wave_plan[2u * wave + 1u] < cap ? p.wave_plan[2u * wave + 1u] : cap;
+  const uint32_t ntiles = held > cur ? held : cur;
+  const uint32_t gd = p.g_mem, gs = p.g_snap;
+  uint32_t *wm = p.mem + (size_t)wave * p.mem_words * 64u;
+  for (uint32_t ti = c; ti < ntiles; ti += p.chunks) {
+    uint32_t *to = wm + (size_t)ti * 4096u;
+    const bool one = cls != wbs::kGather;
+    if (one) {
+      const uint32_t sw = s_src[0] >> 6;
+      const uint32_t rows = p.snap_rows[sw] < p.mem_words ? p.snap_rows[sw] : p.mem_words;
+      if (ti >= rows / wbs::kTile) {   // (uniform over the block)
+        snap_init_tile(p, to, ti, t);
+        continue;
+      }
+      WB_SNAP_SYNC();   // (the previous round's readers of tile)
+      const uint32_t *from = p.snap + p.snap_off[sw] + (size_t)ti * 4096u;
+      for (uint32_t k = 0; k < 4; k++) {
+        const uint32_t x = 4u * (t + 256u * k);
+        const wb_snap_v4 v = *(const wb_snap_v4 *)(from + x);
+        for (uint32_t q = 0; q < 4; q++)
+          tile[snap_elem_lane(x + q, gs) * kSnapPitch + snap_elem_word(x + q, gs)] = v[q];
+      }
+    } else {
+      WB_SNAP_SYNC();
+      const uint32_t l = t >> 2, s = s_src[l], sw = s >> 6, sl = s & 63u;
+      const uint32_t rows = p.snap_rows[sw] < p.mem_words ? p.snap_rows[sw] : p.mem_words;
+      const bool in = ti < rows / wbs::kTile;
+      const uint32_t *from = p.snap + p.snap_off[sw];
+      for (uint32_t j = 0; j < 4; j++) {
+        const uint32_t k = 4u * ((t & 3u) + 4u * j), w = ti * wbs::kTile + k;
+        uint32_t *cell = &tile[l * kSnapPitch + k];
+        if (!in) {
+          for (uint32_t q = 0; q < 4; q++) cell[q] = w + q < p.image_words ? p.image[w + q] : 0u;
+        } else if (gs >= 2) {   // (4 words of a granule: contiguous and 16-byte aligned)
+          const wb_snap_v4 v = *(const wb_snap_v4 *)(from + wbh::lane_word(w, sl, gs));
+          for (uint32_t q = 0; q < 4; q++) cell[q] = v[q];
+        } else {
+          for (uint32_t q = 0; q < 4; q++) cell[q] = from[wbh::lane_word(w + q, sl, gs)];
+        }
+      }
+    }
+    WB_SNAP_SYNC();
+    for (uint32_t k = 0; k < 4; k++) {
+      const uint32_t x = 4u * (t + 256u * k);
+      wb_snap_v4 v;
+      for (uint32_t q = 0; q < 4; q++) {
+        const uint32_t ln = snap_elem_lane(x + q, gd);
+        v[q] = tile[(one ? (s_src[ln] & 63u) : ln) * kSnapPitch + snap_elem_word(x + q, gd)];
+      }
+      *(wb_snap_v4 *)(to + x) = v;
+    }
+  }
+}
+
+// ---- whole-buffer state through the source map ----------------------------------------------
+// thread i of `stride` threads; the destination side is contiguous, the source side a gather
+// of single words (these buffers are small beside memory 0)
+WB_SNAP_FN void snap_rows_body(const SnapRowsParams &p, size_t i, size_t stride) {
+  const size_t per = (size_t)p.count * 64u, total = per * p.nwaves;
+  const uint32_t g = p.g;
+  for (size_t x = i; x < total; x += stride) {
+    const uint32_t w = (uint32_t)(x / per);
+    const size_t r = x % per;
+    const uint32_t l = (uint32_t)(r >> g) & 63u;
+    const size_t k = ((r >> (6u + g)) << g) + (r & ((1u << g) - 1u));
+    uint32_t v = p.fill;
+    if (p.src) {
+      uint32_t s = p.src_of ? p.src_of[(size_t)w * 64u + l] : w * 64u + l;
+      if ((s >> 6) >= p.nwaves) s = w * 64u + l;   // (the host's plan: always in range)
+      v = p.src[(size_t)(s >> 6) * p.words_s * 64u + wbh::lane_word(p.base_s + k, s & 63u, g)];
+    }
+    if (p.ls_fix) {
+      const size_t slot = p.base_d + k;
+      if (slot == LS_RPC) v = 0xFFFFFFFFu;
+      else if (slot == LS_GSP || slot == LS_HBASE) v = 0u;
+    }
+    p.dst[(size_t)w * p.words_d * 64u + wbh::lane_word(p.base_d + k, l, g)] = v;
+  }
+}

@@ -1,0 +1,98 @@
+// snapshot_plan.h -- the planning of instance snapshots that does not touch the device
+// (snapshot.cpp; DESIGN.md "Instance snapshots"). Host-only and free of HIP, so that a
+// stand-alone host program can share it with the library: how many rows of a wave a
+// snapshot holds, where they sit in the packed buffer, which source every destination lane
+// draws from, the class of every destination wave and the tiles a restore visits.
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+#include "snapshot.h"
+
+namespace wbs {
+
+// (rows_of_mark, the rows of a wave that can differ from zero given its highest write mark:
+// snapshot.h, shared with the kernels)
+
+inline uint32_t wave_mark(const uint32_t *marks64) {
+  uint32_t m = 0;
+  for (uint32_t l = 0; l < 64; l++) m = marks64[l] > m ? marks64[l] : m;
+  return m;
+}
+
+// marks: [nwaves][64] write marks (LS_HWM). rows[w] = the rows wave w's snapshot holds,
+// off[w] = the first word of its rows in the packed buffer (rows[w] * 64 words, wave after
+// wave); returns the buffer's words.
+inline uint64_t pack_rows(const uint32_t *marks, uint32_t nwaves, uint32_t image_words, uint32_t mem_words,
+                          std::vector<uint32_t> *rows, std::vector<uint64_t> *off) {
+  rows->assign(nwaves, 0);
+  off->assign(nwaves, 0);
+  uint64_t total = 0;
+  for (uint32_t w = 0; w < nwaves; w++) {
+    (*rows)[w] = rows_of_mark(wave_mark(marks + size_t(w) * 64), image_words, mem_words);
+    (*off)[w] = total;
+    total += uint64_t((*rows)[w]) * 64u;
+  }
+  return total;
+}
+
+// The captured instance that lane `inst` (of nwaves * 64, the last wave's lanes past n
+// included) restarts from. A lane past n never runs; it follows lane 0 of its wave into that
+// lane's source wave, keeping its own lane number, so that it does not turn a broadcast or a
+// permutation within a wave into a gather.
+inline uint32_t source_of(const uint32_t *src_of, uint32_t n, uint32_t inst) {
+  if (!src_of) return inst;
+  if (inst < n) return src_of[inst];
+  return (src_of[inst & ~63u] & ~63u) | (inst & 63u);
+}
+
+enum WaveClass : uint32_t {
+  kIdentity = 0,   // every lane from itself, same granule: tiles are copied as they lie
+  kOneWave = 1,    // every lane from one source wave: its tile is read whole, permuted in LDS
+  kGather = 2,     // lanes from several waves: every lane gathers its source lane's words
+};
+
+struct RestorePlan {
+  std::vector<uint32_t> src;    // [nwaves * 64] source_of every lane
+  std::vector<uint32_t> wave;   // [nwaves][2]: WaveClass, tiles its sources hold (the largest)
+  uint32_t max_tiles = 0;       // the largest of those
+  bool identity = true;         // every wave kIdentity
+};
+
+// snap_rows: [nwaves] rows each captured wave holds (multiples of kTile). Every src_of[i]
+// must be below n (the caller checked).
+inline void plan_restore(const uint32_t *src_of, uint32_t n, uint32_t nwaves, const uint32_t *snap_rows,
+                         bool same_granule, RestorePlan *P) {
+  P->src.resize(size_t(nwaves) * 64);
+  P->wave.assign(size_t(nwaves) * 2, 0);
+  P->max_tiles = 0;
+  P->identity = true;
+  for (uint32_t w = 0; w < nwaves; w++) {
+    bool self = same_granule, one = true;
+    uint32_t tiles = 0;
+    for (uint32_t l = 0; l < 64; l++) {
+      const uint32_t i = w * 64 + l, s = source_of(src_of, n, i);
+      P->src[i] = s;
+      self = self && s == i;
+      one = one && (s >> 6) == (P->src[size_t(w) * 64] >> 6);
+      const uint32_t t = snap_rows[s >> 6] / kTile;
+      tiles = t > tiles ? t : tiles;
+    }
+    const uint32_t cls = self ? kIdentity : one ? kOneWave : kGather;
+    P->wave[2 * size_t(w)] = cls;
+    P->wave[2 * size_t(w) + 1] = tiles;
+    P->max_tiles = tiles > P->max_tiles ? tiles : P->max_tiles;
+    P->identity = P->identity && cls == kIdentity;
+  }
+}
+
+// Tiles a restore visits for a destination wave: up to the larger of what its sources hold
+// (copied, or image / zero for a lane whose own source wave holds less) and the wave's
+// current bound `cur_rows` (rows_of_mark of its marks now: re-initialised).
+inline uint32_t visit_tiles(uint32_t src_tiles, uint32_t cur_rows) {
+  const uint32_t cur = cur_rows / kTile;
+  return src_tiles > cur ? src_tiles : cur;
+}
+
+}  // namespace wbs
