@@ -175,6 +175,11 @@ typedef struct WasmEdge_BatchConfigure {
    * 0 = an eighth of the device's memory). Past it a call ends the instance with 0xB0.
    * Each BatchReset returns the stack to its first depth. */
   uint64_t CallStackMaxBytes;
+  /* Resumable runs (WasmEdge_BatchResume below): 0 = off, Interrupted (0x07) is final and
+   * BatchResume fails with WrongVMWorkflow (0x04). Non-zero: an instance that ends a
+   * BatchRun or BatchResume with 0x07 is suspended on the device, and the frame-save area
+   * is allocated for every module, not only those with imports or growth. */
+  uint32_t Resumable;
 } WasmEdge_BatchConfigure;
 
 #define WASMEDGE_BATCH_PARTITION_BLOCKS 0u
@@ -313,6 +318,45 @@ WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchRun(WasmEdge_BatchContext *Cxt,
 WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchResults(WasmEdge_BatchContext *Cxt, WasmEdge_Value *Returns,
                       const uint32_t ReturnLen, uint8_t *PerInstance, uint64_t *InstrCounts);
+
+/* ---- resumable runs ---------------------------------------------------------------------
+ * With WasmEdge_BatchConfigure::Resumable set, an instance that ends a BatchRun or a
+ * BatchResume with Interrupted (0x07) -- MaxSteps / StepLimit reached, TimeLimitSeconds
+ * passed, WasmEdge_BatchInterrupt -- is SUSPENDED, not lost: it keeps 0x07 in PerInstance
+ * and its count so far in InstrCounts, its returns read zero, and its frame, call stack, pc,
+ * gas total and instance state stay on the device. The reference has no counterpart (its
+ * Interrupted is final), hence the switch.
+ *
+ * BatchResume continues every suspended instance from where it stopped, in one launch
+ * followed by the usual host-import rounds. Every other instance -- finished, trapped,
+ * CostLimitExceeded (0x03), or sat out with NO_CALL / FuncNotFound / FuncSigMismatch -- is
+ * untouched: status, count, returns, memory and gas stay as they were. StepLimit is the new
+ * CUMULATIVE per-instance instruction limit of the invocation, in the units of InstrCounts
+ * (which run on across resumes); 0 = none. A caller slices with k * slice. An instance whose
+ * count already reaches StepLimit is suspended again as it is; one below it retires at least
+ * one instruction. The wall-clock limit starts anew with each call, and a pending interrupt
+ * request is cleared when the call starts, as in BatchRun. With nothing suspended the call
+ * succeeds and launches nothing (*KernelSeconds = 0). BatchResults afterwards works as after
+ * BatchRun; per-instance calls keep their ReturnLens.
+ *
+ * BatchGetSuspendedCount: the suspended instances after the last Run / Resume (a counter
+ * the kernels keep; no status copy), 0 for NULL; a multi-device context sums its shards.
+ *
+ * BatchReset, BatchSetArgs, BatchSetCalls and BatchSnapshotRestore end a suspended
+ * invocation: BatchResume then fails with WrongVMWorkflow (0x04), as it does on a context
+ * that is not Resumable, before any BatchRun, and for NULL. BatchRun ends it too and begins a
+ * new one: what it left suspended is dropped, and a BatchResume after it continues the
+ * instances the new run suspended. BatchSnapshotCreate stays legal
+ * (frames are not captured: restoring such a snapshot equals restoring one taken between
+ * runs). Between slices a caller may read (BatchResults, GetMemory, ReadMemories(Device),
+ * MemoryHash, GlobalGetValue, TableGet*, GetTotalCosts) and write (SetMemory,
+ * WriteMemories(Device), GlobalSetValue, TableSetData); a suspended instance sees the
+ * writes when it continues, as if a host function had made them. Not resumable: a start
+ * function interrupted during BatchReset (0x07 stays the instantiation status) and
+ * CostLimitExceeded. */
+WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchResume(WasmEdge_BatchContext *Cxt, uint64_t StepLimit,
+                                                        double *KernelSeconds);
+WASMEDGE_BATCH_API uint32_t WasmEdge_BatchGetSuspendedCount(const WasmEdge_BatchContext *Cxt);
 
 /* ---- per-instance calls ---------------------------------------------------------------
  * Each instance runs its own export: N independent WasmEdge_VMExecute calls

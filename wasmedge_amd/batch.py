@@ -64,7 +64,7 @@ class _Conf(ctypes.Structure):
                 ("MemoryPoolBytes", ctypes.c_uint64), ("Devices", ctypes.POINTER(ctypes.c_int32)),
                 ("DeviceCount", ctypes.c_uint32), ("Partition", ctypes.c_uint32),
                 ("MultiMemories", ctypes.c_uint32), ("ExtraMemoryReservePages", ctypes.c_uint32),
-                ("CallStackMaxBytes", ctypes.c_uint64)]
+                ("CallStackMaxBytes", ctypes.c_uint64), ("Resumable", ctypes.c_uint32)]
 
 PARTITION_BLOCKS, PARTITION_INTERLEAVE = 0, 1
 
@@ -145,6 +145,7 @@ def lib():
             ("WasmEdge_BatchSetArgs", [vp, _String, vp, u32]),
             ("WasmEdge_BatchReset", [vp, ctypes.POINTER(ctypes.c_double)]),
             ("WasmEdge_BatchRun", [vp, ctypes.POINTER(ctypes.c_double)]),
+            ("WasmEdge_BatchResume", [vp, u64, ctypes.POINTER(ctypes.c_double)]),
             ("WasmEdge_BatchResults", [vp, vp, u32, vp, vp]),
             ("WasmEdge_BatchMemoryHash", [vp, vp]),
             ("WasmEdge_BatchGetMemory", [vp, u32, u32, vp, u32]),
@@ -162,6 +163,8 @@ def lib():
             f.argtypes = args
         L.WasmEdge_BatchGetMemoryPages.restype = u32
         L.WasmEdge_BatchGetMemoryPages.argtypes = [vp, u32]
+        L.WasmEdge_BatchGetSuspendedCount.restype = u32
+        L.WasmEdge_BatchGetSuspendedCount.argtypes = [vp]
         L.WasmEdge_BatchGetInstanceCount.restype = u32
         L.WasmEdge_BatchGetInstanceCount.argtypes = [vp]
         L.WasmEdge_BatchGetCodeSize.restype = u32
@@ -270,12 +273,13 @@ class BatchContext:
                  time_limit=0.0, device=-1, cost_limit=0, host_threads=0, cost_table=None,
                  memory_granule=0, imports=None, tail_call=False, memory_reserve_pages=0,
                  memory_pool_bytes=0, devices=None, partition=PARTITION_BLOCKS, multi_memory=False,
-                 extra_memory_reserve_pages=0, call_stack_max_bytes=0):
+                 extra_memory_reserve_pages=0, call_stack_max_bytes=0, resumable=False):
         """cost_table: gas cost per OpCode (list; missing entries 0), None = unit costs;
         metering is on when cost_limit > 0. max_memory_page 0 = the reference's default
         page limit (65536); memory_reserve_pages / memory_pool_bytes: the device layout of
         grown memory (WasmEdge_BatchConfigure). devices: a list of HIP ordinals (repeats
-        allowed) to spread the instances over from this process, by `partition`."""
+        allowed) to spread the instances over from this process, by `partition`. resumable:
+        instances that end a run with 0x07 are suspended and resume() continues them."""
         L = lib()
         tab = None
         if cost_table is not None:
@@ -287,6 +291,7 @@ class BatchContext:
         conf.MultiMemories = 1 if multi_memory else 0
         conf.ExtraMemoryReservePages = extra_memory_reserve_pages
         conf.CallStackMaxBytes = call_stack_max_bytes
+        conf.Resumable = 1 if resumable else 0
         if devices is not None and len(devices) == 1:
             conf.DeviceOrdinal = devices[0]
         if devices is not None and len(devices) > 1:
@@ -354,6 +359,19 @@ class BatchContext:
         t = ctypes.c_double(0)
         self._check(lib().WasmEdge_BatchRun(self._h, ctypes.byref(t)))
         return t.value
+
+    def resume(self, step_limit=0, timed=True):
+        """Continue the suspended instances (status 0x07) of the last run() / resume() on a
+        resumable context (WasmEdge_BatchResume). step_limit: the new cumulative instruction
+        limit per instance, in the units of results()' counts (0: none). Returns the kernel
+        time (timed=False: 0)."""
+        t = ctypes.c_double(0)
+        self._check(lib().WasmEdge_BatchResume(self._h, step_limit, ctypes.byref(t) if timed else None))
+        return t.value
+
+    def suspended(self):
+        """Instances suspended after the last run() / resume() (WasmEdge_BatchGetSuspendedCount)."""
+        return lib().WasmEdge_BatchGetSuspendedCount(self._h)
 
     def results(self, nret):
         rets = np.zeros((self.n, max(nret, 1)), VALUE_DTYPE)

@@ -381,7 +381,8 @@ uint8_t setup(WasmEdge_BatchContext *C, const uint8_t *wasm, uint32_t len) {
       (!P.xmems.empty() && (!C->xmem.alloc(nw * 64 * size_t(C->xwords) + 64) ||
                             !C->xpages.alloc(C->xpages0.size()))) ||
       (C->frame_hbm && !C->hframe.alloc(nw * size_t(P.total_cells()) * 64)) ||
-      ((P.n_imported || C->grow_host || C->gs_grow || C->tg_grow) && (!C->fsave.alloc(nw * size_t(P.total_cells() + C->gs_lds) * 64) ||
+      (C->conf.Resumable && !C->susp_ctr.alloc(1)) ||
+      ((P.n_imported || C->grow_host || C->gs_grow || C->tg_grow || C->conf.Resumable) && (!C->fsave.alloc(nw * size_t((P.total_cells() ? P.total_cells() : 1) + C->gs_lds) * 64) ||
                         !C->hcall.alloc(C->n) || !C->hbuf.alloc(size_t(C->n) * C->hb_cells))))
     return C->fail(kRuntimeError, "device allocation of instance state failed (" +
                                       std::to_string(nw * size_t(C->mem_words) * 256 >> 20) +
@@ -451,8 +452,9 @@ uint32_t cells_of_value(uint8_t t) { return wb::cells_of(t); }
 constexpr uint32_t kCallsPc = 0xFFFFFFFEu;
 
 // One interpreter launch over every instance: entry_pc with the staged params (or the
-// start function when is_start). Shared by BatchRun and BatchReset.
-uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, bool resume,
+// start function when is_start). Shared by BatchRun, BatchResume and BatchReset. resume
+// (KParams::resume): 0 a fresh invocation, 1 a host-import round, 2 BatchResume's launch.
+uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, uint32_t resume,
                     double *KernelSeconds) {
   const wb::Program &P = C->prog;
   KParams k{};
@@ -512,9 +514,14 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
   k.init_dropped = C->init_dropped;
   k.ls_slots = C->ls_slots;
   k.is_start = is_start ? 1u : 0u;
-  k.resume = resume ? 1u : 0u;
+  k.resume = resume;
   k.hb_cells = C->hb_cells;
-  k.max_steps = C->conf.MaxSteps ? C->conf.MaxSteps : (1ull << 62);
+  // (BatchResume and its host-import rounds: the call's cumulative limit, not MaxSteps)
+  const uint64_t steps = C->inv_resuming ? C->inv_steps : C->conf.MaxSteps;
+  k.max_steps = steps ? steps : (1ull << 62);
+  // resumable contexts: Interrupted lanes park and count themselves (never a start function:
+  // an interrupted instantiation is final)
+  k.suspended = C->conf.Resumable && !is_start ? C->susp_ctr.ptr : nullptr;
   double tl = C->conf.TimeLimitSeconds > 0 ? C->conf.TimeLimitSeconds : 600.0;
   k.max_ticks = uint64_t(tl * 1e8);
   k.sched = C->sched;
@@ -624,15 +631,16 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
 
 // One interpreter invocation over every instance: entry_pc with the staged params (or the
 // start function when is_start), then host-import rounds until no lane is parked.
-// Shared by BatchRun and BatchReset.
-uint8_t launch_exec(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start,
-                    double *KernelSeconds) {
+// Shared by BatchRun, BatchResume (resume: its launch continues the suspended lanes) and
+// BatchReset.
+uint8_t launch_rounds(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, bool resume,
+                      double *KernelSeconds) {
   if (KernelSeconds) *KernelSeconds = 0;
   // (the flag is cleared only after an Interrupt: one stream operation less per run)
   if (C->stop_dirty.exchange(false) &&
       !C->hip_ok(hipMemsetAsync(C->stop, 0, 4, C->stream), "interrupt flag")) return kRuntimeError;
   if (C->parked_h) *C->parked_h = 0u;   // (the previous launch has ended: launch_once syncs)
-  uint8_t e = launch_once(C, entry_pc, is_start, false, KernelSeconds);
+  uint8_t e = launch_once(C, entry_pc, is_start, resume ? 2u : 0u, KernelSeconds);
   if (e || !(C->prog.n_imported || C->grow_host || C->gs_grow || C->tg_grow)) return e;
   for (;;) {
     if (C->parked_h && !__atomic_load_n(C->parked_h, __ATOMIC_ACQUIRE)) return 0;   // none parked
@@ -641,9 +649,24 @@ uint8_t launch_exec(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start,
     const int64_t k = service_host_calls(C);
     if (k < 0) return kRuntimeError;
     if (k == 0) return 0;
-    e = launch_once(C, entry_pc, is_start, true, KernelSeconds);
+    e = launch_once(C, entry_pc, is_start, 1u, KernelSeconds);
     if (e) return e;
   }
+}
+
+// ... and, on a resumable context, the suspended instances it leaves: the device counter
+// zeroed before the first launch and read once after the last round (4 bytes, not N statuses)
+uint8_t launch_exec(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, double *KernelSeconds,
+                    bool resume = false) {
+  const bool count = C->conf.Resumable && !is_start;
+  if (count && !C->hip_ok(hipMemsetAsync(C->susp_ctr.ptr, 0, 4, C->stream), "suspended counter"))
+    return kRuntimeError;
+  const uint8_t e = launch_rounds(C, entry_pc, is_start, resume, KernelSeconds);
+  if (e || !count) return e;
+  // (every launch has ended: launch_once waits for its kernel)
+  if (!C->hip_ok(hipMemcpy(&C->suspended, C->susp_ctr.ptr, 4, hipMemcpyDeviceToHost), "suspended counter"))
+    return kRuntimeError;
+  return 0;
 }
 
 }  // namespace
@@ -769,6 +792,7 @@ WasmEdge_Result WasmEdge_BatchSetArgs(WasmEdge_BatchContext *C, const WasmEdge_S
   C->result_cells = rc;
   C->result_types = t.results;
   C->calls_on = false;   // (back to one function for every instance)
+  C->end_invocation();   // (new staging: a suspended invocation cannot continue)
   return R(0);
 }
 
@@ -860,6 +884,7 @@ WasmEdge_Result WasmEdge_BatchSetCalls(WasmEdge_BatchContext *C, const WasmEdge_
   C->call_status.swap(cstat);
   C->calls_import = import;
   C->calls_on = true;
+  C->end_invocation();
   return R(0);
 }
 
@@ -879,6 +904,7 @@ WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeco
   if (!C->shards.empty()) return wbm::reset(C, KernelSeconds);
   DevScope dev(C);
   const wb::Program &P = C->prog;
+  C->end_invocation();   // (fresh instances: nothing suspended)
   if (C->trial == 2 || C->trial == 4) {   // (layout_trial)
     const uint8_t e = relayout(C, C->trial_mlog[C->trial == 2 ? 1 : 0]);
     if (e) return R(e);
@@ -991,14 +1017,48 @@ WasmEdge_Result WasmEdge_BatchRun(WasmEdge_BatchContext *C, double *KernelSecond
     return R(C->fail(kRuntimeError, "exported function is a host import"));
   const bool measure = C->trial == 1 || C->trial == 3;
   double ks = 0;
-  uint8_t e = launch_exec(C, C->calls_on ? kCallsPc : C->prog.funcs[C->func].entry_pc, false,
-                          KernelSeconds || measure ? &ks : nullptr);
+  C->end_invocation();   // (a suspended invocation ends where the next one starts)
+  C->inv_pc = C->calls_on ? kCallsPc : C->prog.funcs[C->func].entry_pc;
+  uint8_t e = launch_exec(C, C->inv_pc, false, KernelSeconds || measure ? &ks : nullptr);
   if (e) return R(e);
   if (KernelSeconds) *KernelSeconds = ks;
   if (C->trial == 5) C->trial = 1;   // (the warm-up run of the layout trial)
   else if (measure && (e = layout_trial(C, ks))) return R(e);
   C->ran = true;
+  C->inv_live = C->conf.Resumable != 0;
   return R(0);
+}
+
+// Continue the suspended instances of the last invocation (DESIGN.md "Resumable runs"): one
+// launch with KParams::resume = 2 at that invocation's entry pc (kCallsPc with the call
+// table still staged), then the usual host-import rounds, all under StepLimit. The launch
+// takes no wave order and records none, and the layout trial takes nothing from a slice
+// (launch_once skips both for a resume; only BatchRun measures).
+WasmEdge_Result WasmEdge_BatchResume(WasmEdge_BatchContext *C, uint64_t StepLimit, double *KernelSeconds) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!C->shards.empty()) return wbm::resume(C, StepLimit, KernelSeconds);
+  if (!C->conf.Resumable) return R(C->fail(kWrongVMWorkflow, "BatchResume: the context is not Resumable"));
+  if (!C->inv_live) return R(C->fail(kWrongVMWorkflow, "BatchResume: no suspended invocation"));
+  if (KernelSeconds) *KernelSeconds = 0;
+  if (!C->suspended) return R(0);   // nothing to continue: no launch
+  DevScope dev(C);
+  C->inv_resuming = true;
+  C->inv_steps = StepLimit;
+  const uint8_t e = launch_exec(C, C->inv_pc, false, KernelSeconds, true);
+  C->inv_resuming = false;
+  if (e) {
+    C->end_invocation();   // (a device error: the saved state is not to be trusted)
+    return R(e);
+  }
+  return R(0);
+}
+
+uint32_t WasmEdge_BatchGetSuspendedCount(const WasmEdge_BatchContext *C) {
+  if (!C) return 0;
+  uint32_t n = C->inv_live ? C->suspended : 0;
+  for (const WasmEdge_BatchContext *s : C->shards)
+    if (s) n += WasmEdge_BatchGetSuspendedCount(s);
+  return n;
 }
 
 WasmEdge_Result WasmEdge_BatchResults(WasmEdge_BatchContext *C, WasmEdge_Value *Returns,

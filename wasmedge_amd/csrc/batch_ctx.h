@@ -220,6 +220,18 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> calls;
   std::vector<int32_t> call_func;
   std::vector<uint8_t> call_status;
+  // resumable runs (conf.Resumable; DESIGN.md "Resumable runs"): the invocation BatchResume
+  // continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
+  // Run / SnapshotRestore --, its entry pc, the cumulative step limit of the call in
+  // progress (BatchResume's; a Run takes conf.MaxSteps), the device counter the kernel adds
+  // suspended lanes to (KParams::suspended) and its value after the last Run / Resume
+  bool inv_live = false;
+  uint32_t inv_pc = 0;
+  uint64_t inv_steps = 0;
+  bool inv_resuming = false;
+  DevBuf<uint32_t> susp_ctr;
+  uint32_t suspended = 0;
+  void end_invocation() { inv_live = false; suspended = 0; }
   bool ran = false;        // a Run completed since the last Reset (results are valid)
   bool mem_fresh = true;    // memory never initialised: the next Reset writes every page
   // A Reset that skipped its host sync left init kernels queued on `stream` (non-blocking,

@@ -415,11 +415,17 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
   if (p.resume) {
     // continue a lane parked at a host import: frame from fsave, the host function's
     // results (hcall = their cell count, ~0 = the host ended the lane) into its cells
+    // A suspended lane (resumable contexts: hcall = WB_SUSPENDED) is parked the same way
+    // but is not this round's to touch: a service round (resume 1) leaves its resume point
+    // and saved frame as they are, and BatchResume's launch (resume 2) continues only such
+    // lanes, with no host results.
     const uint32_t rpc = LS(LS_RPC);
     const bool parked = status == WB_STATUS_RUNNING && rpc != 0xFFFFFFFFu;
-    const uint32_t nres = parked ? p.hcall[inst] : 0xFFFFFFFFu;
-    active = parked && nres != 0xFFFFFFFFu;
-    if (parked) LS(LS_RPC) = 0xFFFFFFFFu;
+    uint32_t nres = parked ? p.hcall[inst] : 0xFFFFFFFFu;
+    const bool mine = (nres == WB_SUSPENDED) == (p.resume == 2u);
+    if (nres == WB_SUSPENDED) nres = 0;
+    active = parked && mine && nres != 0xFFFFFFFFu;
+    if (parked && mine) LS(LS_RPC) = 0xFFFFFFFFu;
     if (active) {
       pc = rpc;
       gsp = LS(LS_GSP);
@@ -428,6 +434,8 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
       for (uint32_t k = 0; k < gsp && k < S_lds; k++) stk[k << 6] = fs[(size_t)(p.total_cells + k) << 6];
       const uint32_t base = LS(LS_HBASE);
       for (uint32_t k = 0; k < nres; k++) F.set(base + k, p.hbuf[(size_t)inst * p.hb_cells + k]);
+      // (BatchResume: a lane already at the new limit runs nothing and suspends again)
+      if (p.resume == 2u && count >= p.max_steps) status = WB_ERR_INTERRUPTED;
     } else {
       status = WB_STATUS_OK;
     }
@@ -863,12 +871,23 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
   if (active) {
     p.status[inst] = (uint8_t)status;
     p.counts[inst] = count;
-    if (status == WB_ERR_HOST_CALL && fs) {   // park: the host loop takes over
-      if (p.parked) *p.parked = 1u;
+    // resumable contexts: an Interrupted lane parks too -- the budget, clock and stop tests
+    // run at the end of a scheduler round, where pc, count, gsp, frame and cost are the
+    // lane's architectural state -- marked WB_SUSPENDED and counted once per wave
+    // (not an instance whose start function was interrupted: it never runs, LS_ISTATUS)
+    const bool susp = p.suspended && status == WB_ERR_INTERRUPTED && !LS(LS_ISTATUS);
+    if (susp && fs) {
+      const uint64_t sm = __ballot(1);
+      if (lane == (uint32_t)__builtin_ctzll(sm))
+        __hip_atomic_fetch_add(p.suspended, (uint32_t)__builtin_popcountll(sm), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if ((status == WB_ERR_HOST_CALL || susp) && fs) {   // park: the host loop takes over
+      if (p.parked && !susp) *p.parked = 1u;
       LS(LS_RPC) = pc;
       LS(LS_GSP) = gsp;
       LS(LS_HBASE) = ybase;
-      p.hcall[inst] = ycall;
+      p.hcall[inst] = susp ? WB_SUSPENDED : ycall;
       for (uint32_t c = p.global_cells; c < p.total_cells; c++) fs[(size_t)c << 6] = F.get(c);
       for (uint32_t k = 0; k < gsp && k < S_lds; k++) fs[(size_t)(p.total_cells + k) << 6] = stk[k << 6];
       for (uint32_t k = 0; k < p.hb_cells && ybase + k < p.total_cells; k++)

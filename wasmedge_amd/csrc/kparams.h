@@ -55,7 +55,8 @@ struct KParams {
   uint32_t init_dropped;        // data segments dropped after instantiation (bitmask)
   uint32_t ls_slots;            // LS_GLOBALS + global_cells
   uint32_t is_start;            // this launch runs the start function (instantiation)
-  uint32_t resume;              // continue the lanes parked at a host import
+  uint32_t resume;              // 1: continue the lanes parked at a host import (a service
+                                // round); 2: continue the suspended lanes (BatchResume)
   uint32_t hb_cells;
   uint64_t max_steps;           // instruction budget per instance (Interrupted, coarse)
   // gas metering (statistics.h:32,69-91): when cost_off is set, every retired wasm
@@ -124,15 +125,23 @@ struct KParams {
   // the row strides). An entry >= WB_CALL_SKIP: the instance sits the launch out with the
   // status in its low byte (0: no call; FuncNotFound, FuncSigMismatch), like a lane past n.
   const uint32_t *calls;
+  // resumable contexts (WasmEdge_BatchConfigure::Resumable), else NULL: a lane that turns
+  // Interrupted parks as one at a host import does, with WB_SUSPENDED in hcall, and adds
+  // itself here (one atomic per wave) -- the suspended instances of this Run / Resume
+  uint32_t *suspended;
 };
 #define WB_CALL_SKIP 0xFFFFFF00u
+// hcall of a suspended lane (above the import indices, beside dbc.h's WB_GROW_CALL /
+// WB_STACK_CALL): a service round (resume 1) leaves the lane, its resume point and its saved
+// frame alone; only BatchResume's launch (resume 2) continues it
+#define WB_SUSPENDED 0xFFFFFFFCu
 
 // Per-lane instance state that persists across invocations until the next Reset (the
 // reference keeps it in ModuleInstance / MemoryInstance / GlobalInstance): memory size,
 // dropped data segments, instantiation status (a trapped start function fails the
 // instance, module.cpp:160-170), the resume point of a lane parked at a host import
-// (pc, call-stack depth, arg/result cell; pc ~0 = not parked), the write mark, the gas
-// total, then the global cells,
+// or suspended (pc, call-stack depth, arg/result cell; pc ~0 = not parked), the write mark,
+// the gas total, then the global cells,
 // then (per-lane tables only) each table's size and the dropped-elem-segment mask.
 #define LS_PAGES 0u
 #define LS_DROPPED 1u

@@ -232,6 +232,17 @@ WasmEdge_Result run(Ctx *C, double *secs) {
   return r;
 }
 
+// Resume: as Run, every shard on its own thread under the same cumulative limit; the
+// shards' suspended invocations end together (every call that ends one goes to all of them)
+WasmEdge_Result resume(Ctx *C, uint64_t step_limit, double *secs) {
+  std::vector<double> t(C->shards.size(), 0.0);
+  const WasmEdge_Result r = each_parallel(C, [&](Ctx *s) {
+    return WasmEdge_BatchResume(s, step_limit, secs ? &t[s->shard_g] : nullptr);
+  });
+  if (secs) *secs = *std::max_element(t.begin(), t.end());
+  return r;
+}
+
 WasmEdge_Result results(Ctx *C, WasmEdge_Value *rets, uint32_t rlen, uint8_t *st, uint64_t *cnt) {
   std::vector<WasmEdge_Value> rv;
   std::vector<uint8_t> sv;

@@ -18,6 +18,8 @@ WasmEdge_Result set_calls(WasmEdge_BatchContext *C, const WasmEdge_String *names
 WasmEdge_Result return_lens(WasmEdge_BatchContext *C, uint32_t *lens);
 WasmEdge_Result reset(WasmEdge_BatchContext *C, double *secs);
 WasmEdge_Result run(WasmEdge_BatchContext *C, double *secs);
+// BatchResume on every shard (a shard with nothing suspended launches nothing)
+WasmEdge_Result resume(WasmEdge_BatchContext *C, uint64_t step_limit, double *secs);
 WasmEdge_Result results(WasmEdge_BatchContext *C, WasmEdge_Value *rets, uint32_t rlen, uint8_t *st,
                         uint64_t *cnt);
 // bulk transfer with a host buffer: Offsets / Lens / rows sliced, PerInstance gathered

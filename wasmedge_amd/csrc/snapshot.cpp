@@ -281,6 +281,7 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
     C->wasi_lanes.swap(lanes);
   }
   C->ran = false;
+  C->end_invocation();       // (frames are not captured: a suspended invocation ends here)
   C->reset_pending = true;   // host accessors settle() before touching instance state
   if (KernelSeconds) {
     C->reset_pending = false;
