@@ -932,8 +932,6 @@ WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeco
   if (!shrink_stack(C)) return R(kRuntimeError);
   // the whole reserved layout: pages a lane grows into within it must read zero
   const uint32_t init_words = C->mem_words;
-  (void)hipEventRecord(C->ev0, C->stream);
-  if (!pool_reset(C)) return R(kRuntimeError);
   // after a run the memory kernel's write-mark path resets the instance state as well
   const bool fused = P.has_mem && !C->mem_fresh && init_words;
   // ... or, when that kernel is all this Reset launches (4-byte granules, no per-lane
@@ -945,6 +943,11 @@ WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeco
   C->reset_deferred = false;
   const bool defer = fused && C->mlog == 0 && !P.mut_tables && P.xmems.empty() && P.start_func < 0 &&
                      !KernelSeconds && !(C->conf.CostLimit && C->init_exceeded) && !(fre && fre[0] == '0');
+  // a deferred Reset with no pool rows to zero puts nothing on the stream: no events round
+  // nothing either (nobody reads them: the time was not asked for)
+  const bool queues = !defer || C->pool_used;
+  if (queues) (void)hipEventRecord(C->ev0, C->stream);
+  if (!pool_reset(C)) return R(kRuntimeError);
   if (defer) {
     C->reset_deferred = true;
   } else if (P.has_mem &&
@@ -976,7 +979,7 @@ WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeco
                                                 P.mem_min, C->init_dropped, C->init_cost, C->stream),
                            "state init"))
     return R(kRuntimeError);
-  (void)hipEventRecord(C->ev1, C->stream);
+  if (queues) (void)hipEventRecord(C->ev1, C->stream);
   // without a start function and without a request for the time, the next launch on the
   // stream orders after this one: no host round trip (errors surface at the next sync)
   double secs = 0;

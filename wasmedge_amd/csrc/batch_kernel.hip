@@ -947,26 +947,154 @@ __device__ __forceinline__ uint32_t state_word(uint32_t slot, const StateInit &s
   return 0;
 }
 
+// ---- a wave's rows rewritten (Reset): stores issued back to back
+// A row is one word of each of the wave's 64 lanes; `col` is the lane's column of it (row r
+// at col[r << 6]). A store needs no answer, so nothing below waits for one: a loop that
+// loads a row's word and stores it waits for the load and -- gfx950 counts loads and stores
+// in one vmcnt -- for the row before's store as well, a full round trip per row. Here the
+// words of RR_CHUNK rows are fetched first and their stores follow each other; the row
+// counts are wave-uniform (readfirstlane), so every loop is a scalar one.
+#define RR_CHUNK 8u
+// (the constant address space: read-only for the kernel's span, so a uniform index is a
+// scalar load whatever was stored before it -- and it counts in lgkmcnt, not with the stores)
+typedef const __attribute__((address_space(4))) uint32_t *rr_words;
+
+// N rows from q on = 0 / = s[0 .. N): the words first, then the stores back to back
+template <uint32_t N>
+__device__ __forceinline__ void rr_put0(uint32_t *q) {
+#pragma unroll
+  for (uint32_t k = 0; k < N; k++) q[k << 6] = 0u;
+}
+template <uint32_t N>
+__device__ __forceinline__ void rr_put(uint32_t *q, rr_words s) {
+  uint32_t v[N];
+#pragma unroll
+  for (uint32_t k = 0; k < N; k++) v[k] = s[k];
+#pragma unroll
+  for (uint32_t k = 0; k < N; k++) q[k << 6] = v[k];
+}
+
+// rows [r0, r1) of the column = 0: whole chunks, then the rest as 4, 2 and 1 rows
+__device__ __forceinline__ void rr_zero(uint32_t *col, uint32_t r0, uint32_t r1) {
+  uint32_t *q = col + ((size_t)r0 << 6);
+  uint32_t n = r1 - r0;
+  for (; n >= RR_CHUNK; n -= RR_CHUNK, q += RR_CHUNK << 6) rr_put0<RR_CHUNK>(q);
+  if (n & 4u) { rr_put0<4>(q); q += 4u << 6; }
+  if (n & 2u) { rr_put0<2>(q); q += 2u << 6; }
+  if (n & 1u) rr_put0<1>(q);
+}
+
+// rows [0, count) of the column = src[0 .. count), the same words for every lane: a chunk's
+// words by one scalar load, then its stores; nothing past src[count - 1] is read
+__device__ __forceinline__ void rr_uniform(uint32_t *col, const uint32_t *src, uint32_t count) {
+  rr_words s = (rr_words)(uintptr_t)src;
+  uint32_t *q = col;
+  uint32_t n = count;
+  for (; n >= RR_CHUNK; n -= RR_CHUNK, q += RR_CHUNK << 6, s += RR_CHUNK) rr_put<RR_CHUNK>(q, s);
+  if (n & 4u) { rr_put<4>(q, s); q += 4u << 6; s += 4; }
+  if (n & 2u) { rr_put<2>(q, s); q += 2u << 6; s += 2; }
+  if (n & 1u) rr_put<1>(q, s);
+}
+static_assert(RR_CHUNK == 8u, "the rest of a chunk is written as 4, 2 and 1 rows");
+
+// rows [0, count) of a layout of 2^g-word granules (g > 0; count > 0 implies image_words
+// > 0): a lane's word of row r is wb_mem_init_kernel's (r >> g << g) | (i & (2^g - 1)), i =
+// 64 r + lane, so the image words differ by lane and come by vector loads. One chunk's loads
+// are in flight while the chunk before is stored; the only wait is for a chunk's own loads.
+__device__ __forceinline__ void rr_granules(uint32_t *col, uint32_t lane, const uint32_t *image,
+                                            uint32_t image_words, uint32_t count, uint32_t g) {
+  const uint32_t gm = (1u << g) - 1u;
+  // (the loaded words are not looked at here -- that would wait for them at once -- only
+  // which of them lie in the image: bit k of the result)
+  auto fetch = [&](uint32_t (&v)[RR_CHUNK], uint32_t r0) {
+    uint32_t in = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < RR_CHUNK; k++) {
+      const size_t i = (size_t)min(r0 + k, count - 1u) * 64u + lane;
+      const uint32_t word = (uint32_t)(((i >> (6 + g)) << g) | (i & gm));
+      v[k] = image[min(word, image_words - 1u)];   // (no branch round the load)
+      in |= (word < image_words ? 1u : 0u) << k;
+    }
+    return in;
+  };
+  if (!count) return;
+  uint32_t v[RR_CHUNK], nx[RR_CHUNK];
+  uint32_t in = fetch(v, 0), nin = 0;
+  for (uint32_t r = 0; r < count; r += RR_CHUNK) {
+    const bool more = count - r > RR_CHUNK;
+    if (more) nin = fetch(nx, r + RR_CHUNK);
+    // all of v has arrived before its first store: one counted wait, none between the stores
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+#pragma unroll
+    for (uint32_t k = 0; k < RR_CHUNK; k++)
+      if (r + k < count) col[(size_t)(r + k) << 6] = (in >> k) & 1u ? v[k] : 0u;
+    if (more) {
+#pragma unroll
+      for (uint32_t k = 0; k < RR_CHUNK; k++) v[k] = nx[k];
+      in = nin;
+    }
+  }
+}
+
+// The rows of one wave below `rows` (wave-uniform) back to the instantiation image: image
+// words below image_words, zero above -- split once, nothing chosen per row. `wm` = the
+// wave's memory; g as in wb_mem_init_kernel (fused_reset: 0).
+__device__ __forceinline__ void reset_rows(uint32_t *wm, uint32_t lane, uint32_t rows, const uint32_t *image,
+                                           uint32_t image_words, uint32_t g) {
+  uint32_t *const col = wm + lane;
+  uint32_t irows;
+  if (g == 0) {
+    irows = min(rows, image_words);
+    rr_uniform(col, image, irows);
+  } else {
+    // (rows of a granule row that reaches into the image; the rows above hold no image word)
+    const uint64_t gm = (1ull << g) - 1u;
+    irows = (uint32_t)min((uint64_t)rows, ((uint64_t)image_words + gm) & ~gm);
+    rr_granules(col, lane, image, image_words, irows, g);
+  }
+  rr_zero(col, irows, rows);
+}
+
+// Instance state at instantiation (state_word's words) into the lane's column `lw` of its
+// wave's state: the fixed slots straight, the globals and what follows them as uniform rows.
+__device__ __forceinline__ void reset_state(uint32_t *lw, uint32_t ls_slots, const uint32_t *global_init,
+                                            uint32_t init_pages, uint32_t init_dropped, uint64_t init_cost) {
+  const uint32_t cost_lo = (uint32_t)init_cost, cost_hi = (uint32_t)(init_cost >> 32);
+  lw[(size_t)LS_PAGES << 6] = init_pages;
+  lw[(size_t)LS_DROPPED << 6] = init_dropped;
+  lw[(size_t)LS_ISTATUS << 6] = 0u;
+  lw[(size_t)LS_RPC << 6] = 0xFFFFFFFFu;
+  lw[(size_t)LS_GSP << 6] = 0u;
+  lw[(size_t)LS_HBASE << 6] = 0u;
+  lw[(size_t)LS_HWM << 6] = 0u;
+  lw[(size_t)LS_COST << 6] = cost_lo;
+  lw[(size_t)(LS_COST + 1u) << 6] = cost_hi;
+  rr_uniform(lw + ((size_t)LS_GLOBALS << 6), global_init, ls_slots - LS_GLOBALS);
+}
+static_assert(LS_GLOBALS == 9u, "reset_state writes every slot below the globals by name");
+
 // A Reset folded into the launch (KParams::rf_on; batch_api.cpp WasmEdge_BatchReset, 4-byte
 // granules only): before its wave runs, each lane rewrites its own memory words below the
 // wave's write mark (or the image) and its instance state -- wb_mem_init_kernel's
 // write-mark path for one wave, with no kernel of its own. Every lane writes only its own
-// column, so its later loads see the words in program order.
+// column, so its later loads see the words in program order: no wait follows the stores.
 __device__ __forceinline__ void fused_reset(const KParams &p, uint32_t wave, uint32_t lane) {
+  // the Reset's own arguments are read here, from the kernel-argument segment, and not kept
+  // in registers from the kernel's entry through the interpreter
+  typedef const __attribute__((address_space(4))) KParams *rr_kparams;
+  rr_kparams kp = (rr_kparams)__builtin_amdgcn_kernarg_segment_ptr();
+  wave = __builtin_amdgcn_readfirstlane(wave);
   uint32_t *const lw = p.lstate + (size_t)wave * p.ls_slots * 64u + lane;
-  uint32_t m = lw[(size_t)LS_HWM << 6];
+  uint32_t m = lw[(size_t)LS_HWM << 6];   // (read before reset_state overwrites it)
   for (uint32_t o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor(m, o, 64));
+  asm volatile("" : "+s"(kp));   // (opaque from here: the loads below stay below)
+  const uint32_t init_words = kp->rf_init_words, image_words = kp->rf_image_words;
+  m = __builtin_amdgcn_readfirstlane(m);
   const uint64_t hw = ((uint64_t)m + 3u) / 4u;
-  uint32_t rows = (uint32_t)(hw < p.rf_init_words ? hw : p.rf_init_words);
-  if (rows < p.rf_image_words && p.rf_image_words <= p.rf_init_words) rows = p.rf_image_words;
-  uint32_t *const wm = p.mem + (size_t)wave * p.mem_words * 64u + lane;
-  for (uint32_t w = 0; w < rows; w++) wm[(size_t)w << 6] = w < p.rf_image_words ? p.rf_image[w] : 0u;
-  // (state_word's words, from the kernel arguments: no StateInit on the stack)
-  for (uint32_t slot = 0; slot < p.ls_slots; slot++)
-    lw[(size_t)slot << 6] = slot == LS_PAGES ? p.rf_init_pages : slot == LS_DROPPED ? p.rf_init_dropped
-                          : slot == LS_RPC ? 0xFFFFFFFFu : slot == LS_COST ? (uint32_t)p.rf_init_cost
-                          : slot == LS_COST + 1 ? (uint32_t)(p.rf_init_cost >> 32)
-                          : slot >= LS_GLOBALS ? p.rf_global_init[slot - LS_GLOBALS] : 0u;
+  uint32_t rows = (uint32_t)(hw < init_words ? hw : init_words);
+  if (rows < image_words && image_words <= init_words) rows = image_words;
+  reset_rows(p.mem + (size_t)wave * p.mem_words * 64u, lane, rows, kp->rf_image, image_words, 0);
+  reset_state(lw, p.ls_slots, kp->rf_global_init, kp->rf_init_pages, kp->rf_init_dropped, kp->rf_init_cost);
 }
 
 template <bool VF, bool PG>
@@ -1058,21 +1186,18 @@ wb_mem_init_kernel(uint32_t *mem, const uint32_t *image, uint32_t image_words,
          wave += (size_t)gridDim.x * 4u) {
       uint32_t m = ls[((size_t)wave * ls_slots + LS_HWM) * 64u + lane];
       for (uint32_t o = 32; o; o >>= 1) m = max(m, (uint32_t)__shfl_xor(m, o, 64));
+      m = __builtin_amdgcn_readfirstlane(m);   // (wave-uniform: reset_rows' loops are scalar)
       const uint64_t hw = ((uint64_t)m + 3u) / 4u;
       uint32_t rows = (uint32_t)(hw < init_words ? hw : init_words);
       if (rows < image_words && image_words <= init_words) rows = image_words;
       const uint32_t gm = (1u << g) - 1u;
       rows = (rows + gm) & ~gm;
       if (rows > init_words) rows = init_words;
-      uint32_t *wm = mem + wave * mem_words * (size_t)64u;
-      for (size_t i = lane; i < (size_t)rows * 64u; i += 64u) {
-        const uint32_t word = (uint32_t)(((i >> (6 + g)) << g) | (i & ((1u << g) - 1u)));
-        wm[i] = word < image_words ? image[word] : 0u;
-      }
-      if (st.on) {   // (after every lane's mark was read: the shuffle)
-        uint32_t *lw = ls + (size_t)wave * ls_slots * 64u;
-        for (uint32_t i = lane; i < ls_slots * 64u; i += 64u) lw[i] = state_word(i >> 6, st);
-      }
+      const size_t uw = __builtin_amdgcn_readfirstlane((uint32_t)wave);   // (nwaves is 32-bit)
+      reset_rows(mem + uw * mem_words * (size_t)64u, lane, rows, image, image_words, g);
+      if (st.on)   // (after every lane's mark was read: the shuffle)
+        reset_state(ls + uw * ls_slots * 64u + lane, ls_slots, st.global_init, st.init_pages,
+                    st.init_dropped, st.init_cost);
     }
     return;
   }
