@@ -347,8 +347,10 @@ WasmEdge_BatchResults(WasmEdge_BatchContext *Cxt, WasmEdge_Value *Returns,
  * that is not Resumable, before any BatchRun, and for NULL. BatchRun ends it too and begins a
  * new one: what it left suspended is dropped, and a BatchResume after it continues the
  * instances the new run suspended. BatchSnapshotCreate stays legal
- * (frames are not captured: restoring such a snapshot equals restoring one taken between
- * runs). Between slices a caller may read (BatchResults, GetMemory, ReadMemories(Device),
+ * (it captures no frames: restoring such a snapshot equals restoring one taken between
+ * runs, and ends the invocation). BatchSnapshotCreateSuspended (below) captures the
+ * suspended invocation as well; restoring such a snapshot reinstates it, whatever ended it
+ * since, and BatchResume continues it. Between slices a caller may read (BatchResults, GetMemory, ReadMemories(Device),
  * MemoryHash, GlobalGetValue, TableGet*, GetTotalCosts) and write (SetMemory,
  * WriteMemories(Device), GlobalSetValue, TableSetData); a suspended instance sees the
  * writes when it continues, as if a host function had made them. Not resumable: a start
@@ -596,8 +598,9 @@ WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Off
  * total (WasmEdge_BatchGetTotalCosts) and the built-in WASI state of every instance (captured
  * stdout / stderr, exit code, fd table, generator and clock counters; mapped through SrcOf,
  * except that an instance keeps its own index and its own args).
- * Not captured: frames and the call stack (a snapshot is taken between runs, when no
- * instance is parked at a host function), staged arguments and calls, the last run's results
+ * Not captured by SnapshotCreate: frames and the call stack (such a snapshot is taken
+ * between runs, when no instance is parked at a host function; for a suspended invocation
+ * see SnapshotCreateSuspended below), staged arguments and calls, the last run's results
  * (after a restore WasmEdge_BatchResults fails as after a BatchReset, until the next run),
  * externref handles (they live as long as the context) and the memory layout, which a
  * restore neither changes nor depends on: a snapshot stays valid when the granule, the
@@ -617,10 +620,39 @@ WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Off
  * be NULL) = the device time of the restore; NULL: no host synchronisation, the next launch
  * orders after it, as with BatchReset. A snapshot outlives BatchReset and other restores and
  * may be restored any number of times; SnapshotDelete is safe before or after BatchDelete of
- * its context. Not to be called from inside a host function. */
+ * its context. Not to be called from inside a host function.
+ *
+ * SnapshotCreateSuspended: everything SnapshotCreate captures plus the suspended invocation
+ * of a Resumable context (resumable runs, above) -- every instance's frame, call stack and
+ * resume point, its status, instruction count and result row, and the invocation itself
+ * (the function or the call vector, the result types). Legal only while an invocation is
+ * live: after a completed BatchRun / BatchResume and before anything that ends it; otherwise
+ * (NULL, a context that is not Resumable, before any BatchRun, after BatchReset / SetArgs /
+ * SetCalls / a plain restore) NULL with WrongVMWorkflow (0x04). Zero suspended instances is
+ * legal. Device-memory failures as for SnapshotCreate. SnapshotGetSuspendedCount: the
+ * suspended instances the snapshot holds; 0 for NULL and for a snapshot without an
+ * invocation; a multi-device snapshot sums its shards.
+ *
+ * SnapshotRestore of such a snapshot restores the instance state as above and then
+ * reinstates the invocation: instance i continues, at the next BatchResume, exactly as
+ * instance SrcOf[i] would have from the capture; an instance whose source had finished,
+ * trapped or sat the call out is final with the source's status, count and returns and does
+ * not run. BatchGetSuspendedCount then reports the suspended sources under the map,
+ * BatchResults works at once and returns the rows as they stood at the capture (through
+ * SrcOf, as do BatchGetReturnLens and the result types of a call vector), and InstrCounts
+ * continue cumulatively, so the caller goes on with the same k * slice. It is legal whatever
+ * the context did since the capture (BatchReset, runs of other exports, SetCalls, other
+ * restores); a call stack that BatchReset shrank since grows back first (RuntimeError 0x02
+ * with a message when it cannot, all state unchanged). Reset, SetArgs, SetCalls, Run and a
+ * restore of a snapshot without an invocation end it as usual. The staged arguments are not
+ * captured: when the restore maps instances (SrcOf) or the context staged other arguments
+ * since the capture, a BatchRun needs SetArgs / SetCalls first (WrongVMWorkflow otherwise). */
 typedef struct WasmEdge_BatchSnapshot WasmEdge_BatchSnapshot;
 WASMEDGE_BATCH_API WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *Cxt,
                                                                         WasmEdge_Result *Res);
+WASMEDGE_BATCH_API WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreateSuspended(WasmEdge_BatchContext *Cxt,
+                                                                                 WasmEdge_Result *Res);
+WASMEDGE_BATCH_API uint32_t WasmEdge_BatchSnapshotGetSuspendedCount(const WasmEdge_BatchSnapshot *Snap);
 WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *Cxt, const WasmEdge_BatchSnapshot *Snap,
                               const uint32_t *SrcOf, double *KernelSeconds);

@@ -226,6 +226,10 @@ def lib():
         L.WasmEdge_BatchGetEngine.argtypes = [vp]
         L.WasmEdge_BatchSnapshotCreate.restype = vp
         L.WasmEdge_BatchSnapshotCreate.argtypes = [vp, ctypes.POINTER(_Result)]
+        L.WasmEdge_BatchSnapshotCreateSuspended.restype = vp
+        L.WasmEdge_BatchSnapshotCreateSuspended.argtypes = [vp, ctypes.POINTER(_Result)]
+        L.WasmEdge_BatchSnapshotGetSuspendedCount.restype = ctypes.c_uint32
+        L.WasmEdge_BatchSnapshotGetSuspendedCount.argtypes = [vp]
         L.WasmEdge_BatchSnapshotRestore.restype = _Result
         L.WasmEdge_BatchSnapshotRestore.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double)]
         L.WasmEdge_BatchSnapshotGetBytes.restype = u64
@@ -446,10 +450,14 @@ class BatchContext:
         return out, status, counts
 
     # instance snapshots (WasmEdge_BatchSnapshotCreate / Restore)
-    def snapshot(self):
-        """Capture every instance's state as it stands between runs; returns a Snapshot."""
+    def snapshot(self, invocation=False):
+        """Capture every instance's state as it stands between runs; returns a Snapshot.
+        invocation=True (a resumable context after run() / resume()): the suspended invocation
+        as well (WasmEdge_BatchSnapshotCreateSuspended) -- restore() then reinstates it and
+        resume() continues it."""
         res = _Result(0)
-        h = lib().WasmEdge_BatchSnapshotCreate(self._h, ctypes.byref(res))
+        create = lib().WasmEdge_BatchSnapshotCreateSuspended if invocation else lib().WasmEdge_BatchSnapshotCreate
+        h = create(self._h, ctypes.byref(res))
         if not h:
             raise WasmEdgeError(res.Code, lib().WasmEdge_BatchGetLastError(self._h).decode())
         return Snapshot(h)
@@ -696,6 +704,11 @@ class Snapshot:
     def nbytes(self):
         """Device bytes the snapshot holds."""
         return int(lib().WasmEdge_BatchSnapshotGetBytes(self._h)) if self._h else 0
+
+    @property
+    def suspended(self):
+        """Suspended instances the snapshot holds (0 unless taken with invocation=True)."""
+        return int(lib().WasmEdge_BatchSnapshotGetSuspendedCount(self._h)) if self._h else 0
 
     def close(self):
         if getattr(self, "_h", None):

@@ -792,6 +792,7 @@ WasmEdge_Result WasmEdge_BatchSetArgs(WasmEdge_BatchContext *C, const WasmEdge_S
   C->result_cells = rc;
   C->result_types = t.results;
   C->calls_on = false;   // (back to one function for every instance)
+  C->restage = false;
   C->end_invocation();   // (new staging: a suspended invocation cannot continue)
   return R(0);
 }
@@ -884,6 +885,7 @@ WasmEdge_Result WasmEdge_BatchSetCalls(WasmEdge_BatchContext *C, const WasmEdge_
   C->call_status.swap(cstat);
   C->calls_import = import;
   C->calls_on = true;
+  C->restage = false;
   C->end_invocation();
   return R(0);
 }
@@ -1016,6 +1018,9 @@ WasmEdge_Result WasmEdge_BatchRun(WasmEdge_BatchContext *C, double *KernelSecond
   if (!C->shards.empty()) return wbm::run(C, KernelSeconds);
   DevScope dev(C);
   if (C->func < 0 && !C->calls_on) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs not called"));
+  if (C->restage)
+    return R(C->fail(kWrongVMWorkflow, "BatchRun: the restored invocation's arguments are not staged "
+                                       "(BatchSetArgs / BatchSetCalls first)"));
   if (C->calls_on ? C->calls_import : C->prog.funcs[C->func].imported)
     return R(C->fail(kRuntimeError, "exported function is a host import"));
   const bool measure = C->trial == 1 || C->trial == 3;

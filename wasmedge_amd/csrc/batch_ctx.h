@@ -232,6 +232,9 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> susp_ctr;
   uint32_t suspended = 0;
   void end_invocation() { inv_live = false; suspended = 0; }
+  // a restore reinstated a suspended invocation (snapshot.cpp) whose function or arguments the
+  // staged ones no longer match: BatchRun asks for SetArgs / SetCalls first (they clear it)
+  bool restage = false;
   bool ran = false;        // a Run completed since the last Reset (results are valid)
   bool mem_fresh = true;    // memory never initialised: the next Reset writes every page
   // A Reset that skipped its host sync left init kernels queued on `stream` (non-blocking,

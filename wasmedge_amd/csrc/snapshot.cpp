@@ -1,7 +1,10 @@
 // snapshot.cpp -- instance snapshots (WasmEdge_BatchSnapshotCreate / Restore / GetBytes /
 // Delete; DESIGN.md "Instance snapshots"): the state of every instance as it stands between
 // runs, held on the device, and a restore that starts instance i from the captured state of
-// instance SrcOf[i]. The device side is snapshot.hip; the planning that needs no device is
+// instance SrcOf[i]. WasmEdge_BatchSnapshotCreateSuspended (DESIGN.md "Snapshots of suspended
+// runs") also holds the suspended invocation of a resumable context -- frames, call stack,
+// resume points, statuses, counts and result rows --, which a restore reinstates for
+// BatchResume. The device side is snapshot.hip; the planning that needs no device is
 // snapshot_plan.h.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +19,8 @@
 
 extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s);
 extern "C" hipError_t wb_launch_snap_rows(const SnapRowsParams *p, hipStream_t s);
+extern "C" hipError_t wb_launch_snap_stack(const SnapStackParams *p, int kind, hipStream_t s);
+extern "C" hipError_t wb_launch_snap_inst(const SnapInstParams *p, hipStream_t s);
 
 using namespace wbh;
 using Ctx = WasmEdge_BatchContext;
@@ -35,10 +40,32 @@ struct WasmEdge_BatchSnapshot {
   DevBuf<uint32_t> lstate, ltab, xmem, xpages;   // copied whole
   std::vector<wbw::Lane> wasi;
   uint64_t bytes = 0;
+  // the suspended invocation (CreateSuspended). Device: the frame-save rows, the HBM rows of
+  // the call stack that parked lanes own -- rows [0, gs_rows_h[w]) of wave w at word gs_off[w]
+  // of `gs` (snapshot_plan.h pack_stack) --, and the arrays indexed by instance. Host: the
+  // invocation's descriptor and which instances were suspended.
+  bool has_inv = false;
+  uint32_t gs_depth = 0;          // the stack's depth at the capture
+  uint64_t gs_words = 0;
+  std::vector<uint32_t> gs_rows_h;
+  DevBuf<uint32_t> gs, gs_rows, fsave, hcall, results;
+  DevBuf<uint64_t> gs_off, counts;
+  DevBuf<uint8_t> status;
+  std::vector<uint8_t> susp_h;    // [n] 1: suspended (parked with WB_SUSPENDED in hcall)
+  uint32_t suspended = 0;         // their number
+  int func = -1;
+  uint32_t param_cells = 0, result_cells = 0, inv_pc = 0;
+  std::vector<uint8_t> result_types;
+  bool calls_on = false, calls_import = false;
+  std::vector<int32_t> call_func;
+  std::vector<uint8_t> call_status;
+  uint64_t args_fp = 0;           // the staging it ran under (Run after a restore: restage)
   // the last restore's plan and its device copy (kept here so that an untimed restore leaves
   // nothing of its own to free while its kernels run)
   mutable wbs::RestorePlan plan;
   mutable DevBuf<uint32_t> plan_src, plan_wave;
+  mutable std::vector<uint32_t> gs_plan;   // (snapshot_plan.h plan_stack)
+  mutable DevBuf<uint32_t> gs_plan_d;
 };
 using Snap = WasmEdge_BatchSnapshot;
 
@@ -84,7 +111,69 @@ bool copy_whole(Ctx *C, DevBuf<T> *to, const DevBuf<T> &from, size_t count, uint
                    "snapshot");
 }
 
-Snap *create_one(Ctx *C, uint8_t *code) {
+// rows of the call stack per block column: as chunks_for, a tile's worth of rows per step
+uint32_t stack_chunks(uint32_t nwaves, const std::vector<uint32_t> &rows) {
+  uint32_t most = 0;
+  for (uint32_t r : rows) most = std::max(most, (r + wbs::kTile - 1) / wbs::kTile);
+  return chunks_for(nwaves, most);
+}
+
+// The suspended invocation of a resumable context into S (the caller checked inv_live and
+// waited for the stream): every lane's LS_RPC / LS_GSP bound the call-stack rows to hold;
+// the state slots themselves are in S->lstate already.
+bool capture_invocation(Ctx *C, Snap *S) {
+  std::vector<uint32_t> rpc, gsp, hc(C->n);
+  std::vector<uint64_t> off;
+  if (!fetch_slot(C, LS_RPC, &rpc) || !fetch_slot(C, LS_GSP, &gsp)) return false;
+  S->gs_depth = C->gs_depth;
+  S->gs_words = wbs::pack_stack(rpc.data(), gsp.data(), C->n, C->nwaves, C->gs_lds, C->gs_depth, &S->gs_rows_h, &off);
+  if (!S->gs.alloc(size_t(S->gs_words) + 4) || !S->gs_rows.upload(S->gs_rows_h, C->stream) ||
+      !S->gs_off.upload(off, C->stream)) {
+    (void)hipGetLastError();
+    C->last_error = "snapshot: no device memory";
+    return false;
+  }
+  S->bytes += (S->gs_words + 4) * 4 + uint64_t(C->nwaves) * 12;
+  SnapStackParams p{};
+  p.gstack = C->gstack.ptr;
+  p.snap = S->gs.ptr;
+  p.snap_off = S->gs_off.ptr;
+  p.snap_rows = S->gs_rows.ptr;
+  p.snap_words = S->gs_words;
+  p.nwaves = C->nwaves;
+  p.gs_depth = C->gs_depth;
+  p.chunks = stack_chunks(C->nwaves, S->gs_rows_h);
+  if (!C->hip_ok(wb_launch_snap_stack(&p, 0, C->stream), "snapshot")) return false;
+  if (!copy_whole(C, &S->fsave, C->fsave, C->fsave.n, &S->bytes) ||
+      !copy_whole(C, &S->hcall, C->hcall, C->n, &S->bytes) ||
+      !copy_whole(C, &S->status, C->status, C->n, &S->bytes) ||
+      !copy_whole(C, &S->counts, C->counts, C->n, &S->bytes) ||
+      !copy_whole(C, &S->results, C->results, C->results.n, &S->bytes) ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot") ||
+      !C->hip_ok(hipMemcpy(hc.data(), C->hcall.ptr, size_t(C->n) * 4, hipMemcpyDeviceToHost), "snapshot"))
+    return false;
+  S->susp_h.assign(C->n, 0);
+  S->suspended = 0;
+  for (uint32_t i = 0; i < C->n; i++)
+    if (rpc[i] != 0xFFFFFFFFu && hc[i] == WB_SUSPENDED) {
+      S->susp_h[i] = 1;
+      S->suspended++;
+    }
+  S->func = C->func;
+  S->param_cells = C->param_cells;
+  S->result_cells = C->result_cells;
+  S->result_types = C->result_types;
+  S->inv_pc = C->inv_pc;
+  S->calls_on = C->calls_on;
+  S->calls_import = C->calls_import;
+  S->call_func = C->call_func;
+  S->call_status = C->call_status;
+  S->args_fp = C->args_fp;
+  S->has_inv = true;
+  return true;
+}
+
+Snap *create_one(Ctx *C, uint8_t *code, bool inv) {
   DevScope dev(C);
   const wb::Program &P = C->prog;
   *code = kRuntimeError;
@@ -149,6 +238,7 @@ Snap *create_one(Ctx *C, uint8_t *code) {
       !copy_whole(C, &S->xpages, C->xpages, P.xmems.empty() ? 0 : C->xpages0.size(), &S->bytes) ||
       !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot"))
     return nullptr;
+  if (inv && !capture_invocation(C, S.get())) return nullptr;
   S->wasi = C->wasi_lanes;
   S->ctx = C;
   {
@@ -208,16 +298,34 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
     fits = S->tabinfo[2 * t + 1] <= P.tabinfo[2 * t + 1];
   if (!fits) return C->fail(kRuntimeError, "restore: the context's layout cannot hold the snapshot");
   DevScope dev(C);
+  const bool same = S->mlog == C->mlog;
+  const bool planned = SrcOf || !same;
+  if (planned) wbs::plan_restore(SrcOf, C->n, C->nwaves, S->rows_h.data(), same, &S->plan);
+  // a suspended invocation: the call stack deep enough for the rows its sources hold (a Reset
+  // since the capture returned it to its first depth) and the result rows at the captured
+  // stride, before anything of the context's state changes
+  if (S->has_inv) {
+    const uint32_t need = wbs::plan_stack(SrcOf ? S->plan.src.data() : nullptr, C->nwaves, S->gs_rows_h.data(), &S->gs_plan);
+    if (need > C->gs_depth && !grow_stack(C, S->gs_depth))
+      return C->fail(kRuntimeError, "restore: the call stack cannot grow back to the depth of the capture "
+                                    "(device memory, CallStackMaxBytes)");
+    const size_t rn = size_t(C->n) * (S->result_cells ? S->result_cells : 1);
+    if ((SrcOf && !S->gs_plan_d.ptr && !S->gs_plan_d.alloc(S->gs_plan.size())) ||
+        ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))) {
+      (void)hipGetLastError();
+      return C->fail(kRuntimeError, "restore: no device memory");
+    }
+    if (SrcOf && !C->hip_ok(hipMemcpyAsync(S->gs_plan_d.ptr, S->gs_plan.data(), S->gs_plan.size() * 4,
+                                           hipMemcpyHostToDevice, C->stream), "restore"))
+      return kRuntimeError;
+  }
   // A Reset left to the next launch is cancelled, not carried out: the restore re-initialises
   // every row below the waves' current bound itself and writes every state slot, and that
   // launch would otherwise wipe what it restored. A Reset that is queued orders before the
   // restore's kernels on the stream; nothing here reads instance state from the host, so an
   // untimed restore does not wait for it.
   C->reset_deferred = false;
-  const bool same = S->mlog == C->mlog;
-  const bool planned = SrcOf || !same;
   if (planned) {
-    wbs::plan_restore(SrcOf, C->n, C->nwaves, S->rows_h.data(), same, &S->plan);
     if ((!S->plan_src.ptr && !S->plan_src.alloc(S->plan.src.size())) ||
         (!S->plan_wave.ptr && !S->plan_wave.alloc(S->plan.wave.size()))) {
       (void)hipGetLastError();
@@ -253,7 +361,9 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
   if (!C->hip_ok(wb_launch_snap_mem(&p, planned && !S->plan.identity ? 2 : 1, C->stream), "restore"))
     return kRuntimeError;
   // the state slots after memory 0 (whose kernel read the current marks), "not parked"
-  uint8_t e = rows_launch(C, C->lstate.ptr, S->lstate.ptr, src_of, C->ls_slots, S->ls_slots, 0, 0, C->ls_slots, 0, 0, 1);
+  // (a suspended invocation keeps its resume points: LS_RPC / LS_GSP / LS_HBASE as captured)
+  uint8_t e = rows_launch(C, C->lstate.ptr, S->lstate.ptr, src_of, C->ls_slots, S->ls_slots, 0, 0, C->ls_slots, 0, 0,
+                          S->has_inv ? 0 : 1);
   // per-lane tables, table by table: the capacities may have widened since (widen_tables);
   // the slots past the captured capacity are null
   for (uint32_t t = 0; !e && S->tab_words && t < P.ntables; t++) {
@@ -267,6 +377,37 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
   const size_t xs = size_t(C->nwaves) * 64;
   for (size_t k = 0; !e && k < P.xmems.size(); k++)
     e = rows_launch(C, C->xpages.ptr + k * xs, S->xpages.ptr + k * xs, src_of, 1, 1, 0, 0, 1, 0, 0, 0);
+  // the suspended invocation: frame-save rows, the call-stack rows of the sources, and status,
+  // count, hcall and result row of every instance
+  if (!e && S->has_inv) {
+    const uint32_t fw = uint32_t(P.total_cells() ? P.total_cells() : 1) + C->gs_lds;
+    e = rows_launch(C, C->fsave.ptr, S->fsave.ptr, src_of, fw, fw, 0, 0, fw, 0, 0, 0);
+    SnapStackParams k{};
+    k.gstack = C->gstack.ptr;
+    k.snap = S->gs.ptr;
+    k.snap_off = S->gs_off.ptr;
+    k.snap_rows = S->gs_rows.ptr;
+    k.src = S->plan_src.ptr;
+    k.wave_plan = S->gs_plan_d.ptr;
+    k.snap_words = S->gs_words;
+    k.nwaves = C->nwaves;
+    k.gs_depth = C->gs_depth;
+    k.chunks = stack_chunks(C->nwaves, S->gs_rows_h);
+    if (!e && !C->hip_ok(wb_launch_snap_stack(&k, SrcOf ? 2 : 1, C->stream), "restore")) e = kRuntimeError;
+    SnapInstParams q{};
+    q.status_d = C->status.ptr;
+    q.status_s = S->status.ptr;
+    q.counts_d = C->counts.ptr;
+    q.counts_s = S->counts.ptr;
+    q.hcall_d = C->hcall.ptr;
+    q.hcall_s = S->hcall.ptr;
+    q.results_d = C->results.ptr;
+    q.results_s = S->results.ptr;
+    q.src_of = src_of;
+    q.n = C->n;
+    q.result_cells = S->result_cells;
+    if (!e && !C->hip_ok(wb_launch_snap_inst(&q, C->stream), "restore")) e = kRuntimeError;
+  }
   if (e) return e;
   (void)hipEventRecord(C->ev1, C->stream);
   // the host-side WASI lane state through SrcOf; `index` and an instance's own args stay
@@ -281,8 +422,39 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
     C->wasi_lanes.swap(lanes);
   }
   C->ran = false;
-  C->end_invocation();       // (frames are not captured: a suspended invocation ends here)
+  C->end_invocation();       // (a snapshot without frames: a suspended invocation ends here)
   C->reset_pending = true;   // host accessors settle() before touching instance state
+  if (S->has_inv) {
+    // the invocation's descriptor, the per-instance fields through SrcOf; BatchResume
+    // continues it and BatchResults reads the rows as they stood (it does not settle: wait)
+    C->restage = SrcOf || C->args_fp != S->args_fp || C->func != S->func || C->calls_on != S->calls_on;
+    C->func = S->func;
+    C->param_cells = S->param_cells;
+    C->result_cells = S->result_cells;
+    C->result_types = S->result_types;
+    C->calls_on = S->calls_on;
+    C->calls_import = S->calls_import;
+    C->call_func = S->call_func;
+    C->call_status = S->call_status;
+    C->suspended = 0;
+    for (uint32_t i = 0; i < C->n; i++) {
+      const uint32_t s = SrcOf ? SrcOf[i] : i;
+      C->suspended += S->susp_h[s];
+      if (S->calls_on && SrcOf) {
+        C->call_func[i] = S->call_func[s];
+        C->call_status[i] = S->call_status[s];
+      }
+    }
+    C->inv_pc = S->inv_pc;
+    C->inv_live = true;
+    C->ran = true;
+    C->reset_pending = false;
+    if (!C->hip_ok(hipStreamSynchronize(C->stream), "restore")) {
+      C->end_invocation();
+      C->ran = false;
+      return kRuntimeError;
+    }
+  }
   if (KernelSeconds) {
     C->reset_pending = false;
     if (!C->hip_ok(hipStreamSynchronize(C->stream), "restore")) return kRuntimeError;
@@ -295,31 +467,41 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
 
 }  // namespace
 
-extern "C" {
-
-WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *C, WasmEdge_Result *Res) {
+static Snap *create(Ctx *C, WasmEdge_Result *Res, bool inv) {
   if (!C) {
+    if (Res) *Res = R(kWrongVMWorkflow);
+    return nullptr;
+  }
+  // an invocation capture needs a live invocation: a completed Run / Resume of a Resumable
+  // context that nothing has ended since (on every shard: they end together)
+  bool live = C->shards.empty() ? C->conf.Resumable && C->inv_live : true;
+  for (Ctx *s : C->shards) live = live && (!s || (s->conf.Resumable && s->inv_live));
+  if (inv && !live) {
+    C->last_error = C->conf.Resumable ? "SnapshotCreateSuspended: no live invocation (BatchRun / BatchResume first)"
+                                      : "SnapshotCreateSuspended: the context is not Resumable";
     if (Res) *Res = R(kWrongVMWorkflow);
     return nullptr;
   }
   uint8_t code = 0;
   Snap *S = nullptr;
   if (C->shards.empty()) {
-    S = create_one(C, &code);
+    S = create_one(C, &code, inv);
   } else {   // one sub-snapshot per shard
     S = new Snap();
     S->n = C->n;
     S->subs.assign(C->shards.size(), nullptr);
     for (size_t g = 0; g < C->shards.size() && !code; g++) {
       if (!C->shards[g]) continue;
-      S->subs[g] = create_one(C->shards[g], &code);
+      S->subs[g] = create_one(C->shards[g], &code, inv);
       if (code) C->last_error = C->shards[g]->last_error;
       else S->bytes += S->subs[g]->bytes;
+      if (!code) S->suspended += S->subs[g]->suspended;
     }
     if (code) {
       delete_one(S);
       S = nullptr;
     } else {
+      S->has_inv = inv;
       S->ctx = C;
       std::lock_guard<std::mutex> g(wbs::g_mu);
       C->snaps.push_back(S);
@@ -327,6 +509,20 @@ WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *C, W
   }
   if (Res) *Res = R(code);
   return S;
+}
+
+extern "C" {
+
+WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *C, WasmEdge_Result *Res) {
+  return create(C, Res, false);
+}
+
+WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreateSuspended(WasmEdge_BatchContext *C, WasmEdge_Result *Res) {
+  return create(C, Res, true);
+}
+
+uint32_t WasmEdge_BatchSnapshotGetSuspendedCount(const WasmEdge_BatchSnapshot *S) {
+  return S && S->has_inv ? S->suspended : 0;
 }
 
 WasmEdge_Result WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *C, const WasmEdge_BatchSnapshot *S,

@@ -42,6 +42,37 @@ struct SnapMemParams {
   uint32_t chunks;             // blocks per wave; block (w, c) takes tiles c, c + chunks, ...
 };
 
+// The HBM part of the call stack (KParams::gstack, [wave][gs_depth][64] at the 4-byte granule)
+// of a suspended invocation. A snapshot holds rows [0, snap_rows[w]) of wave w -- the rows its
+// parked lanes own -- packed as memory 0's: wave w's rows start at word snap_off[w] of `snap`
+// (snap_words words). The kernels clamp every row count to gs_depth and to the packed buffer.
+struct SnapStackParams {
+  uint32_t *gstack;            // the context's call stack
+  uint32_t *snap;              // the packed rows
+  const uint64_t *snap_off;    // [nwaves] multiples of 64
+  const uint32_t *snap_rows;   // [nwaves]
+  const uint32_t *src;         // [nwaves * 64] source instance of every lane (fork)
+  const uint32_t *wave_plan;   // [nwaves][2]: wbs::WaveClass, rows its sources hold (fork)
+  uint64_t snap_words;
+  uint32_t nwaves, gs_depth;   // gs_depth: rows of a wave in `gstack` now
+  uint32_t chunks;             // blocks per wave; block (w, c) takes 16-byte pieces c * 256 + t, ...
+};
+
+// The arrays indexed by instance (status, counts, hcall, the result rows): instance i from
+// instance src_of[i].
+struct SnapInstParams {
+  uint8_t *status_d;
+  const uint8_t *status_s;
+  uint64_t *counts_d;
+  const uint64_t *counts_s;
+  uint32_t *hcall_d;
+  const uint32_t *hcall_s;
+  uint32_t *results_d;
+  const uint32_t *results_s;   // [n][result_cells] both
+  const uint32_t *src_of;      // [>= n] or NULL: every instance from itself
+  uint32_t n, result_cells;
+};
+
 // Whole-buffer state (instance-state slots, per-lane tables, memories 1..7, their sizes):
 // word base_d + k (k < count) of lane l of wave w, in a [wave][words][64] buffer interleaved
 // in granules of 2^g words, from the same word (at base_s) of its source lane -- or `fill`
@@ -52,4 +83,5 @@ struct SnapRowsParams {
   const uint32_t *src_of;      // [nwaves * 64] or NULL: every lane from itself
   uint32_t nwaves, words_d, words_s, base_d, base_s, count, g, fill;
   uint32_t ls_fix;             // 1: instance state -- LS_RPC / LS_GSP / LS_HBASE "not parked"
+                               // (0 for a snapshot that holds the invocation: kept as captured)
 };

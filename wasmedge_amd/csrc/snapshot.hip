@@ -13,6 +13,12 @@
 //     a tile at a time through LDS;
 //   * wb_snap_rows_kernel: the small whole buffers (instance state, per-lane tables, memories
 //     1..7 and their sizes) through the same source map.
+// A snapshot that holds a suspended invocation (DESIGN.md "Snapshots of suspended runs") adds
+//   * wb_snap_stack_capture_kernel / wb_snap_stack_copy_kernel: the HBM rows of the call stack
+//     that a wave's parked lanes own, packed the same way, out and back as they lie;
+//   * wb_snap_stack_fork_kernel: those rows through the source map, a word gather per lane;
+//   * wb_snap_inst_kernel: status, count, hcall and result row of every instance from its
+//     source's (the frame-save rows go through wb_snap_rows_kernel).
 // The bodies are in snapshot_kernels.inc, which also compiles as host code.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -48,7 +54,41 @@ __global__ void __launch_bounds__(256) wb_snap_rows_kernel(const SnapRowsParams 
   snap_rows_body(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
 }
 
+// a suspended invocation (DESIGN.md "Snapshots of suspended runs"): the HBM rows of the call
+// stack that parked lanes own, and the arrays indexed by instance
+__global__ void __launch_bounds__(256) wb_snap_stack_capture_kernel(const SnapStackParams p) {
+  snap_stack_copy_body(p, blockIdx.x, threadIdx.x, false);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_stack_copy_kernel(const SnapStackParams p) {
+  snap_stack_copy_body(p, blockIdx.x, threadIdx.x, true);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_stack_fork_kernel(const SnapStackParams p) {
+  snap_stack_fork_body(p, blockIdx.x, threadIdx.x);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_inst_kernel(const SnapInstParams p) {
+  snap_inst_body(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
+}
+
 }  // namespace
+
+// kind 0: capture, 1: restore (every wave from itself), 2: restore (through p->src)
+extern "C" hipError_t wb_launch_snap_stack(const SnapStackParams *p, int kind, hipStream_t s) {
+  if (p->nwaves == 0 || p->gs_depth == 0 || p->chunks == 0 || p->snap_words == 0) return hipSuccess;
+  const dim3 grid(p->nwaves * p->chunks), block(256);
+  if (kind == 0) hipLaunchKernelGGL(wb_snap_stack_capture_kernel, grid, block, 0, s, *p);
+  else if (kind == 1) hipLaunchKernelGGL(wb_snap_stack_copy_kernel, grid, block, 0, s, *p);
+  else hipLaunchKernelGGL(wb_snap_stack_fork_kernel, grid, block, 0, s, *p);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t wb_launch_snap_inst(const SnapInstParams *p, hipStream_t s) {
+  if (p->n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wb_snap_inst_kernel, dim3((p->n + 255u) / 256u), dim3(256), 0, s, *p);
+  return hipGetLastError();
+}
 
 // kind 0: capture, 1: restore (copy), 2: restore (gather); p->chunks blocks per wave
 extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s) {

@@ -8,6 +8,8 @@
 // contiguous piece of the wave's region at every granule, moved 16 bytes per thread (a wave's
 // access: 1 KiB contiguous). Element x of a tile's 4096 words under granules of 2^g words is
 // word ((x >> (6 + g)) << g) + (x & (2^g - 1)) of lane (x >> g) & 63 (mem_io.hip).
+// The call-stack bodies (at the end) take the same (wave, chunk) blocks over 16-byte pieces
+// of a wave's rows; the bodies over whole buffers and over instances take a flat thread index.
 
 typedef uint32_t wb_snap_v4 __attribute__((vector_size(16)));
 
@@ -174,5 +176,69 @@ WB_SNAP_FN void snap_rows_body(const SnapRowsParams &p, size_t i, size_t stride)
       else if (slot == LS_GSP || slot == LS_HBASE) v = 0u;
     }
     p.dst[(size_t)w * p.words_d * 64u + wbh::lane_word(p.base_d + k, l, g)] = v;
+  }
+}
+
+// ---- the call stack of a suspended invocation (SnapStackParams) -----------------------------
+// Rows of wave w the packed buffer holds, within the stack's depth now and within the buffer
+// (the host's tables: always so).
+WB_SNAP_FN uint32_t snap_stack_held(const SnapStackParams &p, uint32_t w) {
+  const uint32_t r = p.snap_rows[w] < p.gs_depth ? p.snap_rows[w] : p.gs_depth;
+  return p.snap_off[w] + (uint64_t)r * 64u <= p.snap_words ? r : 0u;
+}
+
+// capture (restore false) and the restore of a wave from itself: rows [0, held) of the wave
+// between the stack and the packed buffer as they lie, 16 bytes per thread
+WB_SNAP_FN void snap_stack_copy_body(const SnapStackParams &p, uint32_t b, uint32_t t, bool restore) {
+  const uint32_t wave = b / p.chunks, c = b % p.chunks;
+  if (wave >= p.nwaves) return;
+  const size_t pieces = (size_t)snap_stack_held(p, wave) * 16u;
+  wb_snap_v4 *live = (wb_snap_v4 *)(p.gstack + (size_t)wave * p.gs_depth * 64u);
+  wb_snap_v4 *held = (wb_snap_v4 *)(p.snap + p.snap_off[wave]);
+  for (size_t i = (size_t)c * 256u + t; i < pieces; i += (size_t)p.chunks * 256u) {
+    if (restore) live[i] = held[i];
+    else held[i] = live[i];
+  }
+}
+
+// restore through the source map: a wave of class kIdentity as above; of any other class,
+// rows [0, the most its sources hold): a thread gathers one row's words of 4 adjacent lanes
+// from their source lanes and stores them as one piece. A lane whose source wave holds fewer
+// rows gets zero there (rows above a lane's depth are never read).
+WB_SNAP_FN void snap_stack_fork_body(const SnapStackParams &p, uint32_t b, uint32_t t) {
+  const uint32_t wave = b / p.chunks, c = b % p.chunks;
+  if (wave >= p.nwaves) return;
+  if (p.wave_plan[2u * wave] == wbs::kIdentity) {
+    snap_stack_copy_body(p, b, t, true);
+    return;
+  }
+  const uint32_t want = p.wave_plan[2u * wave + 1u];
+  const size_t pieces = (size_t)(want < p.gs_depth ? want : p.gs_depth) * 16u;
+  wb_snap_v4 *live = (wb_snap_v4 *)(p.gstack + (size_t)wave * p.gs_depth * 64u);
+  for (size_t i = (size_t)c * 256u + t; i < pieces; i += (size_t)p.chunks * 256u) {
+    const uint32_t r = (uint32_t)(i >> 4), l0 = 4u * ((uint32_t)i & 15u);
+    wb_snap_v4 v;
+    for (uint32_t q = 0; q < 4; q++) {
+      uint32_t s = p.src[(size_t)wave * 64u + l0 + q];
+      if ((s >> 6) >= p.nwaves) s = wave * 64u + l0 + q;   // (the host's plan: always in range)
+      const uint32_t sw = s >> 6;
+      v[q] = r < snap_stack_held(p, sw) ? p.snap[p.snap_off[sw] + (size_t)r * 64u + (s & 63u)] : 0u;
+    }
+    live[i] = v;
+  }
+}
+
+// ---- the arrays indexed by instance (SnapInstParams) -----------------------------------------
+// thread i of `stride` threads: status byte, count, hcall word and result row of instance x
+// from its source's
+WB_SNAP_FN void snap_inst_body(const SnapInstParams &p, size_t i, size_t stride) {
+  for (size_t x = i; x < p.n; x += stride) {
+    size_t s = p.src_of ? p.src_of[x] : x;
+    if (s >= p.n) s = x;   // (the host's plan: always in range)
+    p.status_d[x] = p.status_s[s];
+    p.counts_d[x] = p.counts_s[s];
+    p.hcall_d[x] = p.hcall_s[s];
+    for (uint32_t k = 0; k < p.result_cells; k++)
+      p.results_d[x * p.result_cells + k] = p.results_s[s * p.result_cells + k];
   }
 }

@@ -87,6 +87,65 @@ inline void plan_restore(const uint32_t *src_of, uint32_t n, uint32_t nwaves, co
   }
 }
 
+// ---- the call stack of a suspended invocation (DESIGN.md "Snapshots of suspended runs") -----
+// A lane parked with LS_GSP = g owns HBM rows [0, g - gs_lds) of its wave's call stack
+// (batch_kernel.hip GS_RD / GS_WR: slots below gs_lds are LDS, saved with the frame), and
+// nothing above them is ever read. rpc, gsp: [nwaves][64] LS_RPC / LS_GSP. S_w = the largest
+// max(0, gsp - gs_lds) over the wave's parked lanes (rpc != ~0, instance below n), rounded up
+// to a tile, within the gs_depth rows allocated.
+inline uint32_t stack_rows(const uint32_t *rpc64, const uint32_t *gsp64, uint32_t lanes, uint32_t gs_lds,
+                           uint32_t gs_depth) {
+  uint64_t s = 0;
+  for (uint32_t l = 0; l < lanes && l < 64; l++)
+    if (rpc64[l] != 0xFFFFFFFFu && gsp64[l] > gs_lds && gsp64[l] - gs_lds > s) s = gsp64[l] - gs_lds;
+  s = (s + kTile - 1u) & ~uint64_t(kTile - 1u);
+  return uint32_t(s < gs_depth ? s : gs_depth);
+}
+
+// rows[w] = S_w, off[w] = the first word of wave w's rows in the packed buffer (rows[w] * 64
+// words, wave after wave); returns the buffer's words.
+inline uint64_t pack_stack(const uint32_t *rpc, const uint32_t *gsp, uint32_t n, uint32_t nwaves, uint32_t gs_lds,
+                           uint32_t gs_depth, std::vector<uint32_t> *rows, std::vector<uint64_t> *off) {
+  rows->assign(nwaves, 0);
+  off->assign(nwaves, 0);
+  uint64_t total = 0;
+  for (uint32_t w = 0; w < nwaves; w++) {
+    const uint32_t lanes = n > w * 64u ? (n - w * 64u < 64u ? n - w * 64u : 64u) : 0u;
+    (*rows)[w] = stack_rows(rpc + size_t(w) * 64, gsp + size_t(w) * 64, lanes, gs_lds, gs_depth);
+    (*off)[w] = total;
+    total += uint64_t((*rows)[w]) * 64u;
+  }
+  return total;
+}
+
+// The restore of those rows. src: [nwaves * 64] the source of every lane (RestorePlan::src) or
+// NULL: every lane from itself. wave: [nwaves][2] -- the class (kIdentity: the wave's own rows
+// copied as they lie; else every lane gathers its source lane's word of a row: at the stack's
+// 4-byte granule one source wave or several make the same loads, the rows of one wave merely
+// share cache lines) and the rows its sources hold (the largest: rows of a lane above its own
+// source's are never read and get zero). Returns the largest of those: the depth the
+// context's stack needs.
+inline uint32_t plan_stack(const uint32_t *src, uint32_t nwaves, const uint32_t *stack_rows_of,
+                           std::vector<uint32_t> *wave) {
+  wave->assign(size_t(nwaves) * 2, 0);
+  uint32_t need = 0;
+  for (uint32_t w = 0; w < nwaves; w++) {
+    bool self = true, one = true;
+    uint32_t rows = 0;
+    for (uint32_t l = 0; l < 64; l++) {
+      const uint32_t i = w * 64 + l, s = src ? src[i] : i;
+      self = self && s == i;
+      one = one && (s >> 6) == ((src ? src[size_t(w) * 64] : i) >> 6);
+      const uint32_t r = (s >> 6) < nwaves ? stack_rows_of[s >> 6] : 0u;
+      rows = r > rows ? r : rows;
+    }
+    (*wave)[2 * size_t(w)] = self ? kIdentity : one ? kOneWave : kGather;
+    (*wave)[2 * size_t(w) + 1] = rows;
+    need = rows > need ? rows : need;
+  }
+  return need;
+}
+
 // Tiles a restore visits for a destination wave: up to the larger of what its sources hold
 // (copied, or image / zero for a lane whose own source wave holds less) and the wave's
 // current bound `cur_rows` (rows_of_mark of its marks now: re-initialised).
