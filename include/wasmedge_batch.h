@@ -319,6 +319,70 @@ WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchResults(WasmEdge_BatchContext *Cxt, WasmEdge_Value *Returns,
                       const uint32_t ReturnLen, uint8_t *PerInstance, uint64_t *InstrCounts);
 
+/* ---- device-resident arguments and results ----------------------------------------------
+ * SetArgs and Results for a caller whose inputs are produced, and whose outputs are consumed,
+ * on the device (a torch pipeline, a search loop feeding BatchSnapshotRestore): the values
+ * never cross the host. Between them BatchReset, BatchRun and BatchResume work as ever, and
+ * either call may be mixed with its host variant.
+ *
+ * The device value format is the SLOT form: one value is one 64-bit little-endian slot, a
+ * v128 two slots, low half first. A slot holds the low 64 bits of the WasmEdge_Value.Value
+ * the host variants take or return: i32, f32 and funcref in its low 32 bits (on input the
+ * upper 32 bits are ignored, as BatchSetArgs ignores them; on output they are zero), f32 and
+ * f64 as their bit patterns, a null funcref as 0xFFFFFFFF. A row is the function's values
+ * back to back; Slots is [NumInstances][Stride] uint64 (for torch: an int64 tensor), 8-byte
+ * aligned, Stride counted in slots and at least the slots of a row.
+ *
+ * BatchSetArgsDevice has the semantics of BatchSetArgs: FuncNotFound (0x05) for an unknown
+ * export; FuncSigMismatch (0x83) when ParamLen or ParamTypes -- a HOST array, checked in
+ * place of the tags a device row does not carry -- differ from the function's signature; it
+ * returns to one function for every instance, ends a suspended invocation, and keeps the
+ * device buffers of the arguments and results when their sizes do not change. A function
+ * without parameters is legal with NULL Slots.
+ *
+ * BatchResultsDevice works wherever BatchResults works: after BatchRun or BatchResume, at
+ * once after the restore of a suspended snapshot, after BatchSetArgs as well as after
+ * BatchSetArgsDevice. Row i receives the first min(ReturnLen, result count) values of
+ * instance i; the slots of a row past them and the padding up to Stride are left untouched.
+ * An instance whose status is not 0 (a trap, 0x07 -- suspended or final --, CostLimitExceeded)
+ * gets zeroes in those slots, as BatchResults zeroes its values. Slots may be NULL (no
+ * values). PerInstance (device, [NumInstances] bytes) and InstrCounts (device,
+ * [NumInstances] uint64), each may be NULL, are plain device-to-device copies of what
+ * BatchResults returns in their host namesakes.
+ *
+ * WrongVMWorkflow (0x04), for both calls: a NULL context, a Stride smaller than the row
+ * needs, a misaligned pointer; for SetArgsDevice, NULL Slots with a non-empty row; for
+ * ResultsDevice, no completed run, and per-instance calls (there is no SetCallsDevice:
+ * after BatchSetCalls use BatchResults). RuntimeError (0x02): a function with an externref
+ * parameter or result (wide externrefs are interned on the host: use the host variants); a
+ * multi-device context (one device buffer cannot serve several devices); a buffer this HIP
+ * runtime knows not to be on the context's device or not to hold NumInstances rows. Every
+ * failure leaves the staging, the results and the caller's buffers as they were and sets the
+ * WasmEdge_BatchGetLastError message.
+ *
+ * Ordering, as for the *MemoriesDevice calls: the CALLER makes sure that whatever produced
+ * the buffer has finished before the call (synchronise the stream that wrote it); the library
+ * synchronises its own stream before it returns, so the rows are complete, and after every
+ * host-import round of the run, when ResultsDevice returns.
+ *
+ * The arguments' fingerprint -- it decides whether a learnt longest-first wave order is
+ * reused, and whether BatchRun after the restore of a suspended snapshot asks for a new
+ * staging -- is computed on the device from the staged cells and the function: equal for
+ * equal device arguments, different for different ones. It is NOT the value BatchSetArgs
+ * gives the same arguments: staging the same values once by each path counts as a change
+ * (the wave order is learnt again; a restored invocation wants its arguments staged by the
+ * path that staged them before the capture). Results never depend on it. */
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSetArgsDevice(WasmEdge_BatchContext *Cxt, const WasmEdge_String FuncName,
+                            const enum WasmEdge_ValType *ParamTypes /* host */,
+                            const uint32_t ParamLen, const uint64_t *Slots /* device */,
+                            const uint64_t Stride /* slots per row */);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchResultsDevice(WasmEdge_BatchContext *Cxt, uint64_t *Slots /* device, may be NULL */,
+                            const uint32_t ReturnLen, const uint64_t Stride,
+                            uint8_t *PerInstance /* device [N], may be NULL */,
+                            uint64_t *InstrCounts /* device [N], may be NULL */);
+
 /* ---- resumable runs ---------------------------------------------------------------------
  * With WasmEdge_BatchConfigure::Resumable set, an instance that ends a BatchRun or a
  * BatchResume with Interrupted (0x07) -- MaxSteps / StepLimit reached, TimeLimitSeconds

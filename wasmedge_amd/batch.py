@@ -157,6 +157,8 @@ def lib():
             ("WasmEdge_BatchReadMemories", [vp, vp, u32, vp, u32, vp, u64, vp]),
             ("WasmEdge_BatchWriteMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
             ("WasmEdge_BatchReadMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
+            ("WasmEdge_BatchSetArgsDevice", [vp, _String, vp, u32, vp, u64]),
+            ("WasmEdge_BatchResultsDevice", [vp, vp, u32, u64, vp, vp]),
         ]:
             f = getattr(L, name)
             f.restype = _Result
@@ -268,6 +270,17 @@ def make_values(rows, types):
             out["hi"][i, k] = v >> 64
             out["type"][i, k] = t
     return out
+
+
+def slots_of(types):
+    """Width of a device row of these value types in 64-bit slots (set_args_tensor /
+    results_tensor): one slot per value, two for a v128."""
+    n = 0
+    for t in types:
+        if t not in (I32, I64, F32, F64, V128, FUNCREF, EXTERNREF):
+            raise ValueError("0x%02x is not a value type" % t)
+        n += 2 if t == V128 else 1
+    return n
 
 
 class BatchContext:
@@ -610,6 +623,83 @@ class BatchContext:
         """read_memories into such a tensor (bytes an instance does not fill stay as they
         are). Returns the status array."""
         return self._tensor_io(lib().WasmEdge_BatchReadMemoriesDevice, t, offset, offsets, lens)
+
+    # device-resident arguments and results (WasmEdge_BatchSetArgsDevice / ResultsDevice): rows
+    # of 64-bit slots, one per value and two per v128 (low half first), as int64 tensors
+    def _slot_tensor(self, t, width, dtype, what):
+        """t is a contiguous tensor of torch dtype `dtype` on the device: [n, >= width] (width
+        None: [n]). No torch import of its own: a caller with a tensor has imported it."""
+        import sys
+        torch = sys.modules.get("torch")
+        shape = "[%d]" % self.n if width is None else "[%d, stride >= %d]" % (self.n, width)
+        ok = torch is not None and isinstance(t, torch.Tensor) and t.dtype == getattr(torch, dtype) \
+            and t.is_cuda and t.is_contiguous() and t.shape[0:1] == (self.n,) \
+            and (t.dim() == 1 if width is None else t.dim() == 2 and t.shape[1] >= width)
+        if not ok:
+            raise ValueError("%s: a contiguous torch.%s tensor %s on the device is needed" % (what, dtype, shape))
+        return torch
+
+    def set_args_tensor(self, func, types, t):
+        """set_args from a contiguous torch.int64 tensor [n, stride] on the context's device:
+        row i holds instance i's arguments, one 64-bit slot per value (bit patterns for
+        floats; the upper half of an i32 / f32 / funcref slot is ignored) and two per v128,
+        stride >= slots_of(types); types: the parameters' value types, as make_values takes
+        them. The values never cross the host. A torch build that brings a HIP runtime of its
+        own has to initialise the device (torch.cuda.init()) before the process creates its
+        first BatchContext: started second, that runtime finds no GPU."""
+        types = [int(x) for x in types]
+        width = slots_of(types)
+        if width or t is not None:
+            torch = self._slot_tensor(t, width, "int64", "set_args_tensor")
+            # the library does not know the stream that produced the tensor
+            with torch.cuda.device(t.device):
+                torch.cuda.current_stream().synchronize()
+        tarr = np.array(types, np.uint32)
+        self._check(lib().WasmEdge_BatchSetArgsDevice(
+            self._h, self._name(func), tarr.ctypes.data if len(types) else None, len(types),
+            t.data_ptr() if t is not None and t.numel() else None, t.shape[1] if t is not None else 0))
+        self.func = func
+        self._keep = None
+
+    def results_tensor(self, nret, out=None, status=None, counts=None):
+        """results() into device tensors (WasmEdge_BatchResultsDevice): (out, status, counts).
+        out: a contiguous torch.int64 tensor [n, stride], row i receiving instance i's first
+        nret results in the slot form of set_args_tensor (zeroes when its status is not 0);
+        slots of a row past them keep what they held. status: torch.uint8 [n]; counts:
+        torch.int64 [n]. Each is allocated on the current torch device when None -- out as
+        [n, nret], which fits unless a result is a v128 (two slots): then pass nret as the list
+        of result types, or an out wide enough. The same note on torch initialising the device
+        before the first BatchContext applies as for set_args_tensor."""
+        width = None
+        if not isinstance(nret, int):
+            width = slots_of([int(x) for x in nret])
+            nret = len(nret)
+        if nret < 0:
+            raise ValueError("results_tensor: nret must not be negative")
+        given = [x for x in (out, status, counts) if x is not None]
+        if out is not None:
+            self._slot_tensor(out, width or 0, "int64", "results_tensor: out")
+        if status is not None:
+            self._slot_tensor(status, None, "uint8", "results_tensor: status")
+        if counts is not None:
+            self._slot_tensor(counts, None, "int64", "results_tensor: counts")
+        import torch
+        dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+        if out is None:
+            out = torch.zeros((self.n, nret if width is None else width), dtype=torch.int64, device=dev)
+        if status is None:
+            status = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        if counts is None:
+            counts = torch.zeros(self.n, dtype=torch.int64, device=dev)
+        if out.device != dev or status.device != dev or counts.device != dev:
+            raise ValueError("results_tensor: out, status and counts must be on one device")
+        # the library does not know the stream that will consume (or last wrote) the tensors
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream().synchronize()
+        self._check(lib().WasmEdge_BatchResultsDevice(
+            self._h, out.data_ptr() if out.numel() else None, nret, out.shape[1],
+            status.data_ptr(), counts.data_ptr()))
+        return out, status, counts
 
     # exported tables / globals of one instance (WasmEdge_TableInstance*/GlobalInstance*);
     # inst=None writes every instance

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "args_io.h"
 #include "batch_ctx.h"
 #include "build/srchash.h"
 #include "jit.h"
@@ -1111,6 +1112,180 @@ WasmEdge_Result WasmEdge_BatchResults(WasmEdge_BatchContext *C, WasmEdge_Value *
       }
     }
   }
+  return R(0);
+}
+
+// ---- device-resident arguments and results (args_io.hip; DESIGN.md "Device-resident
+// arguments and results") ----------------------------------------------------------------
+}  // extern "C"
+namespace {
+// Rows [0, n) of `row` bytes, `stride` bytes apart from Buf on, lie inside an allocation on
+// the context's device -- as far as this HIP runtime knows the allocation (hostcall.cpp
+// mem_io: one it does not know, a framework's with a runtime of its own, is the caller's word)
+bool device_rows_ok(WasmEdge_BatchContext *C, const void *Buf, uint64_t row, uint64_t stride, const char *what) {
+  if (!Buf || !row || !C->n) return true;
+  hipPointerAttribute_t at{};
+  void *base = nullptr;
+  size_t size = 0;
+  const bool known = hipPointerGetAttributes(&at, Buf) == hipSuccess && at.type != hipMemoryTypeUnregistered;
+  if (!known) {
+    (void)hipGetLastError();
+    return true;
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != C->device ||
+      hipMemGetAddressRange(&base, &size, const_cast<void *>(Buf)) != hipSuccess) {
+    (void)hipGetLastError();
+    C->fail(kRuntimeError, std::string(what) + ": not a buffer on the context's device");
+    return false;
+  }
+  const uint64_t room = uint64_t(size) - uint64_t(static_cast<const uint8_t *>(Buf) - static_cast<uint8_t *>(base));
+  if (room < row || (C->n > 1 && stride > (room - row) / (C->n - 1))) {
+    C->fail(kRuntimeError, std::string(what) + ": the device buffer is smaller than NumInstances rows");
+    return false;
+  }
+  return true;
+}
+bool has_externref(const std::vector<uint8_t> &types) {
+  return std::find(types.begin(), types.end(), uint8_t(wb::EXTERNREF)) != types.end();
+}
+// the table on the device, uploaded when it differs from the one there (`host`)
+bool upload_map(WasmEdge_BatchContext *C, WasmEdge_BatchContext::DevBuf<uint32_t> &dev, std::vector<uint32_t> &host,
+                std::vector<uint32_t> &map) {
+  if (dev.ptr && host == map) return true;
+  host.clear();   // (nothing valid there until the copy is queued)
+  if (dev.n < map.size() && !dev.alloc(map.size())) {
+    (void)hipGetLastError();
+    C->fail(kRuntimeError, "device allocation failed");
+    return false;
+  }
+  host.swap(map);   // (the copy's source lives as long as the context)
+  return C->hip_ok(hipMemcpyAsync(dev.ptr, host.data(), host.size() * 4, hipMemcpyHostToDevice, C->stream),
+                   "signature table upload");
+}
+}  // namespace
+extern "C" {
+
+WasmEdge_Result WasmEdge_BatchSetArgsDevice(WasmEdge_BatchContext *C, const WasmEdge_String FuncName,
+                                            const enum WasmEdge_ValType *ParamTypes, const uint32_t ParamLen,
+                                            const uint64_t *Slots, const uint64_t Stride) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchSetArgs"));
+  DevScope dev(C);
+  std::string name(FuncName.Buf ? FuncName.Buf : "", FuncName.Length);
+  const int f = wb::find_export(C->prog, name);
+  if (f < 0) return R(C->fail(kFuncNotFound, "function '" + name + "' not found"));
+  const wb::FuncType &t = C->prog.types[C->prog.funcs[f].type];
+  // executor.cpp:88-100, on the type array: a device row carries no tags
+  if (ParamLen != t.params.size()) return R(C->fail(kFuncSigMismatch, "parameter count mismatch"));
+  if (ParamLen && !ParamTypes) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: null ParamTypes"));
+  for (uint32_t k = 0; k < ParamLen; k++)
+    if (uint8_t(ParamTypes[k]) != t.params[k]) return R(C->fail(kFuncSigMismatch, "parameter type mismatch"));
+  if (has_externref(t.params) || has_externref(t.results))
+    return R(C->fail(kRuntimeError, "BatchSetArgsDevice: externref values are interned on the host: use BatchSetArgs"));
+  // cell c of a row is word map[c] of the slot row
+  std::vector<uint32_t> map;
+  uint64_t need = 0;
+  for (uint8_t ty : t.params) {
+    for (uint32_t q = 0; q < cells_of_value(ty); q++) map.push_back(uint32_t(need * 2 + q));
+    need += ty == wb::V128 ? 2 : 1;
+  }
+  const uint32_t pc = uint32_t(map.size());
+  if (need && !Slots) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: null Slots"));
+  if (Stride < need) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Stride is smaller than a row"));
+  if (need && (uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Slots is not 8-byte aligned"));
+  if (need && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Stride out of range"));
+  if (!device_rows_ok(C, Slots, need * 8, Stride * 8, "BatchSetArgsDevice")) return R(kRuntimeError);
+  uint32_t rc = 0;
+  for (uint8_t ty : t.results) rc += cells_of_value(ty);
+  const size_t pn = size_t(C->n) * (pc ? pc : 1), rn = size_t(C->n) * (rc ? rc : 1);
+  if ((C->params.n != pn || !C->params.ptr) && !C->params.alloc(pn))
+    return R(C->fail(kRuntimeError, "device allocation failed"));
+  if ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))
+    return R(C->fail(kRuntimeError, "device allocation failed"));
+  if (!C->args_sum.ptr && !C->args_sum.alloc(1)) return R(C->fail(kRuntimeError, "device allocation failed"));
+  C->args_sum_h = 0;
+  if (pc) {
+    if (!upload_map(C, C->pack_map, C->pack_map_h, map)) return R(kRuntimeError);
+    ArgsPackParams p{};
+    p.slots = Slots;
+    p.word_of = C->pack_map.ptr;
+    p.params = C->params.ptr;
+    p.fp = C->args_sum.ptr;
+    p.stride = Stride;
+    p.n = C->n;
+    p.cells = pc;
+    if (!C->hip_ok(hipMemsetAsync(C->args_sum.ptr, 0, 8, C->stream), "fingerprint") ||
+        !C->hip_ok(wb_launch_args_pack(&p, C->stream), "args pack") ||
+        !C->hip_ok(hipMemcpyAsync(&C->args_sum_h, C->args_sum.ptr, 8, hipMemcpyDeviceToHost, C->stream), "fingerprint"))
+      return R(kRuntimeError);
+  }
+  if (!C->hip_ok(hipStreamSynchronize(C->stream), "args pack")) return R(kRuntimeError);
+  // the function and the cells' order-independent sum (args_io.h): equal for equal device
+  // arguments, not the value BatchSetArgs gives the same arguments
+  C->args_fp = args_fp_mix(~uint64_t(f), 0xA5A5A5A5u) + C->args_sum_h;
+  C->func = f;
+  C->param_cells = pc;
+  C->result_cells = rc;
+  C->result_types = t.results;
+  C->calls_on = false;   // (back to one function for every instance)
+  C->restage = false;
+  C->end_invocation();   // (new staging: a suspended invocation cannot continue)
+  return R(0);
+}
+
+WasmEdge_Result WasmEdge_BatchResultsDevice(WasmEdge_BatchContext *C, uint64_t *Slots, const uint32_t ReturnLen,
+                                            const uint64_t Stride, uint8_t *PerInstance, uint64_t *InstrCounts) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchResults"));
+  if (C->calls_on)
+    return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: per-instance calls have no device rows: use BatchResults"));
+  if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
+  DevScope dev(C);
+  // word w of the written part of a row is result cell map[w] (or zero)
+  std::vector<uint32_t> map;
+  uint32_t cell = 0;
+  for (uint32_t k = 0; Slots && k < ReturnLen && k < C->result_types.size(); k++) {
+    const uint8_t ty = C->result_types[k];
+    if (ty == wb::EXTERNREF)
+      return R(C->fail(kRuntimeError, "BatchResultsDevice: externref values are interned on the host: use BatchResults"));
+    const uint32_t nc = cells_of_value(ty);
+    for (uint32_t q = 0; q < nc; q++) map.push_back(cell++);
+    if (nc == 1) map.push_back(kArgsNoCell);
+  }
+  const uint64_t need = map.size() / 2;
+  if (Stride < need) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Stride is smaller than a row"));
+  if (need && (uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Slots is not 8-byte aligned"));
+  if (need && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Stride out of range"));
+  if (InstrCounts && (uintptr_t(InstrCounts) & 7u))
+    return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: InstrCounts is not 8-byte aligned"));
+  if (!device_rows_ok(C, Slots, need * 8, Stride * 8, "BatchResultsDevice") ||
+      !device_rows_ok(C, PerInstance, 1, 1, "BatchResultsDevice") ||
+      !device_rows_ok(C, InstrCounts, 8, 8, "BatchResultsDevice"))
+    return R(kRuntimeError);
+  // (every launch and host-import round of the run has ended: launch_once waits for its
+  // kernel, a restore of a suspended invocation for its own)
+  if (need) {
+    const uint32_t words = uint32_t(map.size());
+    if (!upload_map(C, C->unpack_map, C->unpack_map_h, map)) return R(kRuntimeError);
+    ArgsUnpackParams p{};
+    p.results = C->results.ptr;
+    p.status = C->status.ptr;
+    p.cell_of = C->unpack_map.ptr;
+    p.slots = Slots;
+    p.stride = Stride;
+    p.n = C->n;
+    p.cells = C->result_cells;
+    p.words = words;
+    if (!C->hip_ok(wb_launch_args_unpack(&p, C->stream), "results unpack")) return R(kRuntimeError);
+  }
+  if (PerInstance && !C->hip_ok(hipMemcpyAsync(PerInstance, C->status.ptr, C->n, hipMemcpyDeviceToDevice, C->stream), "status"))
+    return R(kRuntimeError);
+  if (InstrCounts && !C->hip_ok(hipMemcpyAsync(InstrCounts, C->counts.ptr, size_t(C->n) * 8, hipMemcpyDeviceToDevice,
+                                               C->stream), "counts"))
+    return R(kRuntimeError);
+  if (!C->hip_ok(hipStreamSynchronize(C->stream), "results unpack")) return R(kRuntimeError);
   return R(0);
 }
 

@@ -220,6 +220,14 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> calls;
   std::vector<int32_t> call_func;
   std::vector<uint8_t> call_status;
+  // device-resident arguments and results (WasmEdge_BatchSetArgsDevice / ResultsDevice,
+  // args_io.h): the per-signature tables on the device with the host copies they were
+  // uploaded from (a call with the same signature uploads nothing), and the device word the
+  // pack kernel sums the arguments' fingerprint into, with the host word it is read back to
+  DevBuf<uint32_t> pack_map, unpack_map;
+  std::vector<uint32_t> pack_map_h, unpack_map_h;
+  DevBuf<uint64_t> args_sum;
+  uint64_t args_sum_h = 0;
   // resumable runs (conf.Resumable; DESIGN.md "Resumable runs"): the invocation BatchResume
   // continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
   // Run / SnapshotRestore --, its entry pc, the cumulative step limit of the call in
