@@ -4087,6 +4087,10 @@ JitKnobs jit::read_knobs() {
   k.fwd_lazy = on("WB_FWD_LAZY");
   k.fwd_loop = on("WB_FWD_LOOP");
   k.fwd_tail = k.fwd_loop && on("WB_FWD_TAIL");
+  k.fwd_count = k.fwd_tail && on("WB_FWD_COUNT");
+  const char *fue = getenv("WB_FWD_UNROLL");
+  const int fu = fue ? atoi(fue) : 0;
+  k.fwd_unroll = fu == 1 || fu == 2 || fu == 4 ? uint32_t(fu) : kFwdUnroll;
   k.ret_pf = on("WB_RET_PF");
   k.brt_thread = on("WB_BRT_THREAD");
   k.trip_fwd = on("WB_TRIP_FWD");
@@ -4302,6 +4306,196 @@ struct RunCompile {
     d.l("s_mov_b32 %s, 0", TRIPS);
     return d.o;
   }
+
+  // Counted trips (WB_FWD_COUNT). A hoisted loop whose back edge compares an i32
+  // induction cell (written once per trip in the c / p pair, as i + constant) with a
+  // limit the pair never writes: where every lane of the group holds the same i and the
+  // same n, Lhd also knows how many further trips surely take the back edge, clamps TRIPS
+  // to that number (so CNT, cnt_fix and every way out stay as they are) and, with `unroll`
+  // trips or more to go, runs them in a copy of the block (Lfc, after the pair) that holds
+  // the trips' vector code back to back and counts TRIPS down once per pass: no compare,
+  // no read of VCC, no branch inside a pass. What is left (fewer than `unroll` trips)
+  // runs in the tested loop, which leaves, runs out of budget and flushes as before.
+  struct Counted {
+    bool ok = false;
+    int kind = 0;            // 0 i <u n, 1 i <s n, 2 i != n
+    uint32_t icell = 0, ncell = 0;
+    bool nimm = false;       // the limit is a constant (nval)
+    uint32_t nval = 0;
+    uint32_t step = 0;       // > 0; down: i - step (ne only)
+    bool down = false;
+  };
+  const std::string *c_text = nullptr;   // the c copy's code (p's job: jit_source)
+
+  // the instruction that writes `icell` in R's body and p's, if it is the only one, adds a
+  // constant in place and nothing there writes the limit cell (the callee's cells lie at
+  // the call's L and above, where neither may be)
+  bool counted_cells(const JitRun &rr, uint32_t icell, bool has_n, uint32_t ncell, uint32_t L,
+                     int64_t *step) const {
+    const uint32_t fb = P.global_cells;
+    if (icell < fb || icell >= L || (has_n && (ncell < fb || ncell >= L || ncell == icell))) return false;
+    int nw = 0;
+    std::vector<uint32_t> w;
+    auto one = [&](const DInstr &I) {
+      const bool ex = written_exact(I, &w);
+      for (uint32_t x : w) {
+        if (has_n && x == ncell) return false;
+        if (x != icell) continue;
+        const uint16_t o = op_of(I);
+        if (!ex || (o != OP_I32_ADD_I && o != OP_I32_SUB_I) || (I.w1 & 0xFFFFu) != icell) return false;
+        *step = o == OP_I32_ADD_I ? int64_t(int32_t(I.w3)) : -int64_t(int32_t(I.w3));
+        nw++;
+      }
+      return true;
+    };
+    for (uint32_t i = 0; i + 1 < rr.len; i++)
+      if (!one(P.code[rr.pc + i])) return false;
+    for (uint32_t i = 1; i + 1 < r.len; i++)
+      if (!one(P.code[r.pc + i])) return false;
+    return nw == 1;
+  }
+
+  Counted counted_edge() const {
+    Counted c;
+    auto lo = pl.loop_of.find(k);
+    if (!kn.fwd_count || !hoist || var != 2 || cost || lo == pl.loop_of.end() || !c_text) return c;
+    const JitRun &rr = runs[lo->second];
+    const uint32_t L = P.code[rr.pc + rr.len - 1].w1 & 0xFFFFu;
+    static const uint16_t neg[10] = {1, 0, 8, 9, 6, 7, 4, 5, 2, 3};
+    uint16_t kk;
+    uint32_t a, b;
+    bool bimm = false;
+    if (lop == OP_BR_IF || lop == OP_BR_UNLESS) {   // the compare right before it
+      if (r.len < 3) return c;
+      const DInstr &C = P.code[r.pc + r.len - 2];
+      const uint16_t co = op_of(C);
+      const uint32_t cc = C.w2 & 0xFFFFu;
+      a = C.w1 & 0xFFFFu;
+      if (cc != (last.w1 & 0xFFFFu) || cc == a) return c;
+      if (co >= OP_I32_EQ && co <= OP_I32_GE_U) {
+        kk = uint16_t(co - OP_I32_EQ);
+        b = C.w1 >> 16;
+        if (cc == b) return c;
+      } else if (co >= OP_I32_EQ_I && co <= OP_I32_GE_U_I) {
+        kk = uint16_t(co - OP_I32_EQ_I);
+        b = C.w3;
+        bimm = true;
+      } else {
+        return c;
+      }
+      if (lop == OP_BR_UNLESS) kk = neg[kk];
+    } else if (lop >= OP_BR_EQ_I && lop <= OP_BR_GE_U_I) {
+      kk = uint16_t(lop - OP_BR_EQ_I);
+      a = last.w1 & 0xFFFFu;
+      b = uint32_t(int32_t(int16_t(last.w1 >> 16)));
+      bimm = true;
+    } else if (lop >= OP_BR_EQ && lop <= OP_BR_GE_U) {
+      kk = uint16_t(lop - OP_BR_EQ);
+      a = last.w1 & 0xFFFFu;
+      b = last.w1 >> 16;
+    } else {
+      return c;
+    }
+    // taken while i < n (either operand order) or i != n
+    bool swap = false;
+    if (kk == 2 || kk == 3) c.kind = kk == 3 ? 0 : 1;
+    else if ((kk == 4 || kk == 5) && !bimm) { c.kind = kk == 5 ? 0 : 1; swap = true; }
+    else if (kk == 1) c.kind = 2;
+    else return c;
+    int64_t step = 0;
+    for (int tries = 0; tries < 2 && !c.ok; tries++, swap = !swap) {
+      if (swap && bimm) break;
+      c.icell = swap ? b : a;
+      c.ncell = swap ? a : b;
+      c.nimm = bimm;
+      c.nval = bimm ? b : 0;
+      c.ok = counted_cells(rr, c.icell, !bimm, c.ncell, L, &step);
+      if (c.kind != 2) break;   // (!=: either operand may be the counter)
+    }
+    if (!c.ok) return c;
+    c.down = step < 0;
+    c.step = uint32_t(step < 0 ? -step : step);
+    c.ok = step != 0 && c.step < 0x80000000u && (c.kind == 2 || step > 0);
+    return c;
+  }
+
+  // the vector lines of one trip (the c copy's code, then p's up to its tail), or "" when
+  // the block holds anything else: a scalar line, a branch to a stub, a memory access
+  std::string counted_trip(const std::string &p_body) const {
+    std::string out;
+    for (const std::string *s : {c_text, &p_body})
+      for (size_t at = 0; at < s->size();) {
+        size_t nl = s->find('\n', at);
+        if (nl == std::string::npos) nl = s->size();
+        const std::string ln = s->substr(at, nl - at);
+        at = nl + 1;
+        if (ln.empty() || ln[0] == '.' || ln.back() == ':') continue;
+        if (ln.compare(0, 2, "v_") != 0 || ln.compare(0, 7, "v_cmpx_") == 0 ||
+            ln.compare(0, 10, "v_readlane") == 0 || ln.compare(0, 15, "v_readfirstlane") == 0 ||
+            ln.find("exec") != std::string::npos)
+          return "";
+        out += ln + "\n";
+      }
+    return out;
+  }
+
+  // Lhd's part (after the budget's TRIPS, before they are added to CNT) and the counted
+  // copy; vi / vn: the registers the back edge's compare reads
+  void counted_code(Em &x, const Counted &c, const std::string &vi, const std::string &vn,
+                    const std::string &trip, const std::string &head) {
+    const uint32_t U = kn.fwd_unroll;
+    const std::string fc = "Lfc" + K, slow = "Lhn" + K;
+    // uniform under EXEC (the group)?
+    x.l("v_readfirstlane_b32 s68, %s", vi.c_str());
+    if (c.nimm) x.l("s_mov_b32 s69, 0x%x", c.nval);
+    else x.l("v_readfirstlane_b32 s69, %s", vn.c_str());
+    x.l("s_nop 1");
+    x.l("v_cmp_eq_u32_e32 vcc, s68, %s", vi.c_str());
+    x.l("s_cmp_eq_u64 vcc, exec");
+    x.l("s_cbranch_scc0 %s", slow.c_str());
+    if (!c.nimm) {
+      x.l("v_cmp_eq_u32_e32 vcc, s69, %s", vn.c_str());
+      x.l("s_cmp_eq_u64 vcc, exec");
+      x.l("s_cbranch_scc0 %s", slow.c_str());
+    }
+    // s69 = the trips (i + step * j for j = 1..) that surely take the back edge:
+    // <: (n - 1 - i) / step when i < n, else 0 (no wrap: i + step * j stays below n);
+    // !=: ((n - i - 1) mod 2^32) / step (step * j < (n - i) mod 2^32 cannot reach n)
+    if (c.kind == 2) {
+      if (c.down) x.l("s_sub_u32 s69, s68, s69");
+      else x.l("s_sub_u32 s69, s69, s68");
+      x.l("s_sub_u32 s69, s69, 1");
+    } else {
+      if (c.kind == 1) {   // (signed: both onto the unsigned scale)
+        x.l("s_xor_b32 s68, s68, 0x80000000");
+        x.l("s_xor_b32 s69, s69, 0x80000000");
+      }
+      x.l("s_sub_u32 s69, s69, s68");
+      x.l("s_cselect_b32 s69, 0, s69");
+      x.l("s_sub_u32 s69, s69, 1");
+      x.l("s_cselect_b32 s69, 0, s69");
+    }
+    if (c.step > 1) x.l("s_mul_hi_u32 s69, s69, 0x%x", uint32_t((1ull << 32) / c.step));
+    x.l("s_min_u32 %s, %s, s69", TRIPS, TRIPS);
+    x.l("s_mul_i32 s68, %s, 0x%x", TRIPS, trip_cnt);
+    x.l("s_add_u32 s65, s65, s68");
+    x.l("s_sub_u32 s68, %s, %u", TRIPS, U);   // (SCC: fewer than U)
+    cond_jump(x, head, "Lhr" + K);
+    x.l("s_mov_b32 %s, s68", TRIPS);
+    long_jump(x, fc, "Lhf" + K);
+    x.l("%s:", slow.c_str());
+    // (the caller's lines follow: TRIPS to CNT, into the tested loop)
+    Em y(t);
+    y.l(".p2align 6");
+    y.l("%s:", fc.c_str());   // TRIPS = the trips left after this pass
+    for (uint32_t q = 0; q < U; q++) y.o += trip;
+    y.l("s_sub_u32 %s, %s, %u", TRIPS, TRIPS, U);
+    y.l("s_cbranch_scc0 %s", fc.c_str());
+    y.l("s_add_u32 %s, %s, %u", TRIPS, TRIPS, U);
+    long_jump(y, head, "Lfq" + K);
+    counted = y.o;
+  }
+  std::string counted;   // the counted copy, placed after Lhd's code
 
   // The dirty words (F registers) to memory, under the current exec (the lanes that ran
   // the trip): vector code only -- no scalar register, SCC or VCC changes. R raised the
@@ -4960,6 +5154,18 @@ struct RunCompile {
     // (a tight loop's p copy: the back edge enters the c copy)
     const bool hoisted = hoist && var == 2 && lop != OP_JMP && ix.has(tgt);
     const std::string head = hoisted ? "Lb" + std::to_string(ix.at(tgt)) + copy_sfx(ix.at(tgt)) : "";
+    // counted trips: the edge, and the trip's vector code (at most 64 KiB of it a pass)
+    Counted ce = hoisted ? counted_edge() : Counted();
+    std::string ctrip, cvi, cvn;
+    if (ce.ok) {
+      ctrip = counted_trip(e.o);
+      const size_t lines = size_t(std::count(ctrip.begin(), ctrip.end(), '\n'));
+      ce.ok = lines > 0 && lines * kn.fwd_unroll * 8 <= 65536;
+    }
+    if (ce.ok) {
+      cvi = e.V(ce.icell);
+      if (!ce.nimm) cvn = e.V(ce.ncell);
+    }
     if (lop != OP_JMP) {
       if (cmp_any) {   // VCC = the lanes whose any_true is 1
         if (lop == OP_BR_UNLESS) e.l("s_not_b64 vcc, vcc");
@@ -4987,10 +5193,11 @@ struct RunCompile {
         x.l("s_sub_u32 s68, s68, 1");
         x.l("s_mul_hi_u32 %s, s68, 0x%x", TRIPS,
             uint32_t(std::min<uint64_t>(0xFFFFFFFFull, (1ull << 32) / trip_cnt)));
+        if (ce.ok) counted_code(x, ce, cvi, cvn, ctrip, head);
         x.l("s_mul_i32 s68, %s, 0x%x", TRIPS, trip_cnt);
         x.l("s_add_u32 s65, s65, s68");
         long_jump(x, head, "Lhq" + K);
-        extra += x.o;
+        extra += x.o + counted;
       }
       e.l("s_and_b64 %s, vcc, exec", T2);
       e.l("s_cbranch_scc0 %s", nt.c_str());    // no lane takes it
@@ -5160,12 +5367,15 @@ std::string jit_source(const Program &P, const std::vector<JitRun> &runs, uint32
   if (simt) body += simt_sched(t, hybrid, depth_pick);
   const SimtCtx ctx{t, kn, ix, runs, pl, nob, sx, hybrid, depth_pick};
   std::string cold;   // a copy c's out-of-line code: after the p copy it falls through into
+  std::string c_text; // ... and its code, which p's counted copy repeats (counted_trip)
   for (const auto &job : pl.jobs) {
     RunCompile rc(ctx, job.first, job.second);
+    if (job.second == 2) rc.c_text = &c_text;
     if (!rc.compile()) return "";   // jit_runs only picks compilable instructions
     body += rc.e.o;
     if (job.second != 1) body += cold;
     cold = job.second == 1 ? rc.cold : std::string();
+    c_text = job.second == 1 ? rc.e.o : std::string();
   }
   if (hybrid) body += trip_source(t, kn, ix, runs, true);
   body = resolve_jumps(body);

@@ -1,6 +1,6 @@
 // jit_hooks.cpp -- test hooks of the run compiler (CPU tests call them through the
 // library; the product path never does) with their own debugging knobs: WB_JIT_LIST,
-// WB_JIT_DUMP / WB_JIT_DUMP_SIMT / WB_JIT_DUMP_TRIP, WB_JIT_CHECK_PAGES.
+// WB_JIT_DUMP / WB_JIT_DUMP_SIMT / WB_JIT_DUMP_TRIP, WB_JIT_CHECK_PAGES, WB_JIT_CHECK_COST.
 #include <cstdio>
 #include <cstdlib>
 
@@ -18,7 +18,18 @@ extern "C" __attribute__((visibility("default"))) int wb_jit_check(const uint8_t
                                                                    char *err, uint32_t errlen) {
   wb::Program P;
   uint8_t ec = 0;
-  std::string e = wb::load_program(wasm, len, P, &ec, false, nullptr, true, true);
+  // WB_JIT_CHECK_COST=1: as a metered context compiles them (unit costs, plain runs only)
+  const char *mc = getenv("WB_JIT_CHECK_COST");
+  const bool metered = mc && mc[0] == '1';
+  std::string e = wb::load_program(wasm, len, P, &ec, metered, nullptr, true, true);
+  std::vector<uint32_t> cost_off;
+  std::vector<uint64_t> cost_pool;
+  const wb::JitCost jc{&cost_off, &cost_pool, 1};
+  if (e.empty() && metered) {
+    const std::vector<uint64_t> tab(65536, 1ull);
+    bool exceeded = false;
+    wb::build_cost_pool(P, tab.data(), ~0ull, cost_off, cost_pool, &exceeded);
+  }
   std::vector<wb::JitRun> runs;
   if (e.empty() && P.total_cells() > TC_VF_CELLS) e = "frame too large for V frames";
   // extra memories laid out at their minimum sizes (batch_api.cpp reserves more for grown ones)
@@ -63,14 +74,14 @@ extern "C" __attribute__((visibility("default"))) int wb_jit_check(const uint8_t
     }
     // every flavour: plain runs, SIMT scheduling (KParams::simt, its own run choice) and
     // trip mode (its own run choice too)
-    for (int simt = 0; simt < 3 && e.empty(); simt++) {
+    for (int simt = 0; simt < (metered ? 1 : 3) && e.empty(); simt++) {
       if (simt) runs = wb::jit_runs(P, tc, true, simt == 2);
       if (runs.empty()) continue;
       std::vector<char> obj;
       // (a memory below kMadPages unless WB_JIT_CHECK_PAGES says otherwise: the 32-bit
       // granule addresses of trip stages assembled too)
       const char *cp = getenv("WB_JIT_CHECK_PAGES");
-      const std::string src = wb::jit_source(P, runs, glog, nullptr, simt != 0, simt == 2, &xinfo,
+      const std::string src = wb::jit_source(P, runs, glog, metered ? &jc : nullptr, simt != 0, simt == 2, &xinfo,
                                              P.divergent_xmem ? 5u : 0u, cp ? uint32_t(atoi(cp)) : wb::jit::kMadPages);
       if (const char *dump = getenv(simt == 2 ? "WB_JIT_DUMP_TRIP" : simt ? "WB_JIT_DUMP_SIMT" : "WB_JIT_DUMP"))
         if (FILE *f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }

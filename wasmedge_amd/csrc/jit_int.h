@@ -14,6 +14,7 @@ namespace jit {
 // granule address fits 32 bits (granule_addr)
 constexpr uint32_t kMadPages = 1000;
 constexpr uint32_t kTripScan = 4;   // trip mode: scan iterations per trip (trip_scan_stage)
+constexpr uint32_t kFwdUnroll = 1;  // counted trips: trips per pass of the counted copy (RunCompile::counted_edge)
 
 // Every environment variable the code generator reads, each an A/B or debugging aid (results
 // never depend on them). read_knobs() fills one per jit_source call -- tests set these
@@ -35,6 +36,8 @@ struct JitKnobs {
   bool fwd_lazy;       // WB_FWD_LAZY=0: a forwarding copy's stores go to memory every trip
   bool fwd_loop;       // WB_FWD_LOOP=0: the copies keep their stack check, jump and second count
   bool fwd_tail;       // WB_FWD_TAIL=0: a tight loop tests LOW, OTHER and the count limit every trip
+  bool fwd_count;      // WB_FWD_COUNT=0: no counted copy of a tight loop's block (off with WB_FWD_TAIL)
+  uint32_t fwd_unroll; // WB_FWD_UNROLL=n: trips per pass of the counted copy (1, 2 or 4; default kFwdUnroll)
   bool ret_pf;         // WB_RET_PF=0: POST_CALL never reads the RET's record along
   bool brt_thread;     // WB_BRT_THREAD=0: a JMP onto a br_table's run does not take the table
   bool trip_fwd;       // WB_TRIP_FWD=0: no trip-mode load cache
