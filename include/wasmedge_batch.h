@@ -352,8 +352,8 @@ WasmEdge_BatchResults(WasmEdge_BatchContext *Cxt, WasmEdge_Value *Returns,
  *
  * WrongVMWorkflow (0x04), for both calls: a NULL context, a Stride smaller than the row
  * needs, a misaligned pointer; for SetArgsDevice, NULL Slots with a non-empty row; for
- * ResultsDevice, no completed run, and per-instance calls (there is no SetCallsDevice:
- * after BatchSetCalls use BatchResults). RuntimeError (0x02): a function with an externref
+ * ResultsDevice, no completed run, and per-instance calls (their rows differ in signature:
+ * BatchCallsResultsDevice below reads them). RuntimeError (0x02): a function with an externref
  * parameter or result (wide externrefs are interned on the host: use the host variants); a
  * multi-device context (one device buffer cannot serve several devices); a buffer this HIP
  * runtime knows not to be on the context's device or not to hold NumInstances rows. Every
@@ -382,6 +382,68 @@ WasmEdge_BatchResultsDevice(WasmEdge_BatchContext *Cxt, uint64_t *Slots /* devic
                             const uint32_t ReturnLen, const uint64_t Stride,
                             uint8_t *PerInstance /* device [N], may be NULL */,
                             uint64_t *InstrCounts /* device [N], may be NULL */);
+
+/* ---- device-resident per-instance calls -------------------------------------------------
+ * BatchSetCalls and its results (below, "per-instance calls") for a caller whose call vector
+ * and arguments are produced on the device -- "reset the finished environments, step the
+ * others" without a trip through the host. The names, and optionally their signatures, are
+ * host arrays of NumFuncs entries; FuncOf and the rows are device buffers.
+ *
+ * BatchSetCallsDevice has the semantics of BatchSetCalls. FuncOf is a DEVICE array
+ * [NumInstances] of indices into FuncNames or WASMEDGE_BATCH_NO_CALL. Slots is
+ * [NumInstances][Stride] in the slot form above: row i holds the parameters of
+ * FuncNames[FuncOf[i]] back to back from slot 0 (one slot per value, two for a v128, the upper
+ * half of an i32 / f32 / funcref slot ignored); what a row holds past them is not read. Per
+ * instance: NO_CALL gives status 0 and the instance does not run; a name that is no exported
+ * function gives FuncNotFound (0x05); with ParamTypes given (a host array of NumFuncs host
+ * arrays, with ParamLens their lengths; both NULL: the module's signatures are taken as they
+ * are), a ParamLens[j] / ParamTypes[j] that differs from function j's signature gives every
+ * instance naming j FuncSigMismatch (0x83). None of the three runs, and its state stays
+ * untouched. A named export that is a host import fails BatchRun (RuntimeError) only when some
+ * instance calls it, as after BatchSetCalls.
+ *
+ * WrongVMWorkflow (0x04): a NULL context; NULL FuncOf, or NULL FuncNames with NumFuncs != 0;
+ * exactly one of ParamTypes / ParamLens NULL; a Stride smaller than the widest parameter row
+ * among the names that resolve; NULL Slots while a resolved function has parameters; a
+ * misaligned pointer (8 bytes for Slots, 4 for FuncOf); some FuncOf[i] that is neither NO_CALL
+ * nor < NumFuncs (the message names the lowest such i). RuntimeError (0x02): a named function
+ * with an externref parameter or result, called or not; a multi-device context; a buffer this
+ * HIP runtime knows not to be on the context's device or to be too small. Every failure leaves
+ * the previous staging (still runnable), the results and the caller's buffers as they were and
+ * sets the WasmEdge_BatchGetLastError message. A successful call ends a suspended invocation
+ * and keeps the device buffers when their sizes do not change.
+ *
+ * BatchCallsResultsDevice works wherever BatchResults works after a per-instance staging:
+ * after BatchRun / BatchResume, at once after the restore of a suspended snapshot that holds a
+ * call vector, after BatchSetCalls as well as after BatchSetCallsDevice. Row i of Slots gets
+ * exactly Width slots: its function's result slots first, then zeroes; an instance whose
+ * status is not 0, or that sat the run out, gets Width zeroes; the padding from Width to
+ * Stride is untouched. ReturnLens[i] (device, uint32) is what BatchGetReturnLens gives;
+ * PerInstance and InstrCounts are device-to-device copies as for BatchResultsDevice. Each of
+ * the four may be NULL (with NULL Slots, Width and Stride are not looked at).
+ * WrongVMWorkflow (0x04), nothing written: a NULL context; no per-instance staging (a uniform
+ * one: use BatchResultsDevice); no completed run; Stride < Width; a Width smaller than the
+ * widest result row among the staging's functions; a misaligned pointer. RuntimeError (0x02):
+ * a multi-device context; a wrong-device or short buffer; a function with an externref result
+ * (possible only after the host BatchSetCalls).
+ *
+ * Ordering and the fingerprint: as for the calls above. The fingerprint covers FuncOf's
+ * outcome per instance and every staged cell; it is not the value BatchSetCalls gives the same
+ * vector. */
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSetCallsDevice(WasmEdge_BatchContext *Cxt, const WasmEdge_String *FuncNames,
+                             const uint32_t NumFuncs /* host */,
+                             const enum WasmEdge_ValType *const *ParamTypes /* host [NumFuncs], may be NULL */,
+                             const uint32_t *ParamLens /* host [NumFuncs], NULL iff ParamTypes is */,
+                             const uint32_t *FuncOf /* DEVICE [NumInstances] */,
+                             const uint64_t *Slots /* DEVICE [NumInstances][Stride] */,
+                             const uint64_t Stride);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchCallsResultsDevice(WasmEdge_BatchContext *Cxt, uint64_t *Slots /* device, may be NULL */,
+                                 const uint32_t Width, const uint64_t Stride,
+                                 uint32_t *ReturnLens /* device [N], may be NULL */,
+                                 uint8_t *PerInstance /* device [N], may be NULL */,
+                                 uint64_t *InstrCounts /* device [N], may be NULL */);
 
 /* ---- resumable runs ---------------------------------------------------------------------
  * With WasmEdge_BatchConfigure::Resumable set, an instance that ends a BatchRun or a

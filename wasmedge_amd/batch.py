@@ -159,6 +159,8 @@ def lib():
             ("WasmEdge_BatchReadMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
             ("WasmEdge_BatchSetArgsDevice", [vp, _String, vp, u32, vp, u64]),
             ("WasmEdge_BatchResultsDevice", [vp, vp, u32, u64, vp, vp]),
+            ("WasmEdge_BatchSetCallsDevice", [vp, ctypes.POINTER(_String), u32, vp, vp, vp, vp, u64]),
+            ("WasmEdge_BatchCallsResultsDevice", [vp, vp, u32, u64, vp, vp, vp]),
         ]:
             f = getattr(L, name)
             f.restype = _Result
@@ -281,6 +283,28 @@ def slots_of(types):
             raise ValueError("0x%02x is not a value type" % t)
         n += 2 if t == V128 else 1
     return n
+
+
+def call_names(funcs, types=None):
+    """The host arguments of WasmEdge_BatchSetCallsDevice: (names, FuncNames array, ParamTypes
+    pointer or None, ParamLens pointer or None, what has to stay alive for the call). types:
+    None, or one list of value types per name."""
+    funcs = list(funcs)
+    if not all(isinstance(f, str) for f in funcs):
+        raise ValueError("funcs must be export names")
+    names = [f.encode() for f in funcs]
+    arr = (_String * max(len(names), 1))(*[_String(len(b), b) for b in names])
+    if types is None:
+        return names, arr, None, None, (names, arr)
+    types = [[int(x) for x in row] for row in types]
+    if len(types) != len(funcs):
+        raise ValueError("types must hold one list of value types per name")
+    for row in types:
+        slots_of(row)   # (ValueError for what is no value type)
+    rows = [np.array(row, np.uint32) for row in types]
+    ptrs = (ctypes.c_void_p * max(len(rows), 1))(*[r.ctypes.data if len(r) else None for r in rows])
+    lens = np.array([len(r) for r in rows] + [0], np.uint32)
+    return names, arr, ctypes.cast(ptrs, ctypes.c_void_p), lens.ctypes.data, (names, arr, rows, ptrs, lens)
 
 
 class BatchContext:
@@ -700,6 +724,73 @@ class BatchContext:
             self._h, out.data_ptr() if out.numel() else None, nret, out.shape[1],
             status.data_ptr(), counts.data_ptr()))
         return out, status, counts
+
+    # device-resident per-instance calls (WasmEdge_BatchSetCallsDevice / CallsResultsDevice)
+    def set_calls_tensor(self, funcs, func_of, rows, types=None):
+        """set_calls from device tensors: funcs = the export names; func_of: a contiguous
+        torch.int32 tensor [n] on the context's device, instance i's index into funcs or -1 (no
+        call); rows: a contiguous torch.int64 tensor [n, stride], row i holding the arguments
+        of funcs[func_of[i]] in the slot form of set_args_tensor from slot 0 on, or None when
+        nothing takes parameters; types: None (the module's signatures are taken as they are)
+        or one list of value types per name, checked against the module (a difference gives
+        the instances naming that function 0x83). Neither tensor crosses the host. The same
+        note on torch initialising the device before the first BatchContext applies as for
+        set_args_tensor."""
+        names, arr, tptrs, tlens, keep = call_names(funcs, types)
+        torch = self._slot_tensor(func_of, None, "int32", "set_calls_tensor: func_of")
+        if rows is not None:
+            self._slot_tensor(rows, 0, "int64", "set_calls_tensor: rows")
+            if rows.device != func_of.device:
+                raise ValueError("set_calls_tensor: func_of and rows must be on one device")
+        # the library does not know the stream that produced the tensors
+        with torch.cuda.device(func_of.device):
+            torch.cuda.current_stream().synchronize()
+        self._check(lib().WasmEdge_BatchSetCallsDevice(
+            self._h, arr, len(names), tptrs, tlens, func_of.data_ptr(),
+            rows.data_ptr() if rows is not None and rows.numel() else None,
+            rows.shape[1] if rows is not None else 0))
+        self.func = None
+        self._keep = None
+
+    def calls_results_tensor(self, width, out=None, lens=None, status=None, counts=None):
+        """results() / return_lens() after set_calls or set_calls_tensor into device tensors
+        (WasmEdge_BatchCallsResultsDevice): (out, lens, status, counts). out: a contiguous
+        torch.int64 tensor [n, stride >= width]; row i receives exactly `width` slots, its
+        function's result slots first and then zeroes (all zeroes when its status is not 0 or
+        it sat the run out); width must cover the widest result row of the staged functions.
+        lens: torch.int32 [n] (each function's result count); status: torch.uint8 [n]; counts:
+        torch.int64 [n]. Each is allocated on the current torch device when None, out as
+        [n, width]."""
+        if not isinstance(width, int) or isinstance(width, bool) or width < 0:
+            raise ValueError("calls_results_tensor: width must be a non-negative int")
+        given = [x for x in (out, lens, status, counts) if x is not None]
+        if out is not None:
+            self._slot_tensor(out, width, "int64", "calls_results_tensor: out")
+        if lens is not None:
+            self._slot_tensor(lens, None, "int32", "calls_results_tensor: lens")
+        if status is not None:
+            self._slot_tensor(status, None, "uint8", "calls_results_tensor: status")
+        if counts is not None:
+            self._slot_tensor(counts, None, "int64", "calls_results_tensor: counts")
+        import torch
+        dev = given[0].device if given else torch.device("cuda", torch.cuda.current_device())
+        if out is None:
+            out = torch.zeros((self.n, width), dtype=torch.int64, device=dev)
+        if lens is None:
+            lens = torch.zeros(self.n, dtype=torch.int32, device=dev)
+        if status is None:
+            status = torch.zeros(self.n, dtype=torch.uint8, device=dev)
+        if counts is None:
+            counts = torch.zeros(self.n, dtype=torch.int64, device=dev)
+        if any(x.device != dev for x in (out, lens, status, counts)):
+            raise ValueError("calls_results_tensor: out, lens, status and counts must be on one device")
+        # the library does not know the stream that will consume (or last wrote) the tensors
+        with torch.cuda.device(dev):
+            torch.cuda.current_stream().synchronize()
+        self._check(lib().WasmEdge_BatchCallsResultsDevice(
+            self._h, out.data_ptr() if out.numel() else None, width, out.shape[1],
+            lens.data_ptr(), status.data_ptr(), counts.data_ptr()))
+        return out, lens, status, counts
 
     # exported tables / globals of one instance (WasmEdge_TableInstance*/GlobalInstance*);
     # inst=None writes every instance

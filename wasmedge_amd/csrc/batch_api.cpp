@@ -884,6 +884,9 @@ WasmEdge_Result WasmEdge_BatchSetCalls(WasmEdge_BatchContext *C, const WasmEdge_
   C->result_types.clear();
   C->call_func.swap(cfunc);
   C->call_status.swap(cstat);
+  C->call_host_ok = true;    // (calls_io: the device copy of call_func is stale)
+  C->call_dev_ok = false;
+  C->calls_shape();
   C->calls_import = import;
   C->calls_on = true;
   C->restage = false;
@@ -895,6 +898,7 @@ WasmEdge_Result WasmEdge_BatchGetReturnLens(WasmEdge_BatchContext *C, uint32_t *
   if (!C || !ReturnLens) return R(kWrongVMWorkflow);
   if (!C->shards.empty()) return wbm::return_lens(C, ReturnLens);
   if (!C->calls_on && C->func < 0) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs / BatchSetCalls not called"));
+  if (C->calls_on && !C->calls_mirror()) return R(kRuntimeError);
   for (uint32_t i = 0; i < C->n; i++)
     ReturnLens[i] = !C->calls_on ? uint32_t(C->result_types.size())
                     : C->call_func[i] < 0 ? 0u
@@ -1076,6 +1080,7 @@ WasmEdge_Result WasmEdge_BatchResults(WasmEdge_BatchContext *C, WasmEdge_Value *
   if (!C) return R(kWrongVMWorkflow);
   if (!C->shards.empty()) return wbm::results(C, Returns, ReturnLen, PerInstance, InstrCounts);
   if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
+  if (C->calls_on && Returns && ReturnLen && !C->calls_mirror()) return R(kRuntimeError);
   std::vector<uint8_t> st(C->n);
   if (!C->hip_ok(hipMemcpy(st.data(), C->status.ptr, C->n, hipMemcpyDeviceToHost), "status"))
     return R(kRuntimeError);
@@ -1279,6 +1284,236 @@ WasmEdge_Result WasmEdge_BatchResultsDevice(WasmEdge_BatchContext *C, uint64_t *
     p.cells = C->result_cells;
     p.words = words;
     if (!C->hip_ok(wb_launch_args_unpack(&p, C->stream), "results unpack")) return R(kRuntimeError);
+  }
+  if (PerInstance && !C->hip_ok(hipMemcpyAsync(PerInstance, C->status.ptr, C->n, hipMemcpyDeviceToDevice, C->stream), "status"))
+    return R(kRuntimeError);
+  if (InstrCounts && !C->hip_ok(hipMemcpyAsync(InstrCounts, C->counts.ptr, size_t(C->n) * 8, hipMemcpyDeviceToDevice,
+                                               C->stream), "counts"))
+    return R(kRuntimeError);
+  if (!C->hip_ok(hipStreamSynchronize(C->stream), "results unpack")) return R(kRuntimeError);
+  return R(0);
+}
+
+// ---- device-resident per-instance calls (calls_io.hip; DESIGN.md "Device-resident
+// per-instance calls") -------------------------------------------------------------------
+}  // extern "C"
+namespace {
+template <typename T>
+void swap_bufs(WasmEdge_BatchContext::DevBuf<T> &a, WasmEdge_BatchContext::DevBuf<T> &b) {
+  std::swap(a.ptr, b.ptr);
+  std::swap(a.n, b.n);
+}
+template <typename T>
+bool sized(WasmEdge_BatchContext::DevBuf<T> &b, size_t count) {
+  return (b.ptr && b.n == count) || b.alloc(count);
+}
+}  // namespace
+extern "C" {
+
+// BatchSetCalls from a device FuncOf and device slot rows. The host resolves the NumFuncs
+// names into a table; one kernel turns FuncOf and the rows into the call table, the cells and
+// call_fn in the spare buffers and reduces the fingerprint, the lowest invalid FuncOf index and
+// the "an import is called" flag into 16 bytes, read back with the call's one synchronise. A
+// valid vector swaps the spare buffers in; an invalid one leaves the live staging as it was.
+WasmEdge_Result WasmEdge_BatchSetCallsDevice(WasmEdge_BatchContext *C, const WasmEdge_String *FuncNames,
+                                             const uint32_t NumFuncs, const enum WasmEdge_ValType *const *ParamTypes,
+                                             const uint32_t *ParamLens, const uint32_t *FuncOf,
+                                             const uint64_t *Slots, const uint64_t Stride) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchSetCalls"));
+  if (!FuncOf || (NumFuncs && !FuncNames))
+    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null FuncOf / FuncNames"));
+  if ((ParamTypes == nullptr) != (ParamLens == nullptr))
+    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: ParamTypes and ParamLens go together"));
+  DevScope dev(C);
+  const wb::Program &P = C->prog;
+  // the per-name table (calls_io.h), then the names' word_of maps
+  std::vector<uint32_t> tab(size_t(NumFuncs) * kCallsFnWords + 1, 0), maps;
+  uint64_t widest = 0;
+  uint32_t pc = 0, rc = 0, res_slots = 0;
+  for (uint32_t j = 0; j < NumFuncs; j++) {
+    uint32_t *row = &tab[size_t(j) * kCallsFnWords];
+    const std::string name(FuncNames[j].Buf ? FuncNames[j].Buf : "", FuncNames[j].Length);
+    const int f = wb::find_export(P, name);
+    row[kCallsFnEntry] = WB_CALL_SKIP | kFuncNotFound;
+    row[kCallsFnFunc] = 0xFFFFFFFFu;
+    if (f < 0) continue;
+    const wb::FuncInfo &F = P.funcs[f];
+    const wb::FuncType &t = P.types[F.type];
+    if (has_externref(t.params) || has_externref(t.results))
+      return R(C->fail(kRuntimeError, "BatchSetCallsDevice: '" + name + "' takes or returns an externref, which is "
+                                      "interned on the host: use BatchSetCalls"));
+    std::vector<uint32_t> map;
+    uint64_t need = 0;
+    for (uint8_t ty : t.params) {
+      for (uint32_t q = 0; q < cells_of_value(ty); q++) map.push_back(uint32_t(need * 2 + q));
+      need += ty == wb::V128 ? 2 : 1;
+    }
+    widest = std::max(widest, need);
+    // executor.cpp:88-100, on the type arrays: a device row carries no tags
+    bool ok = true;
+    if (ParamTypes) {
+      ok = ParamLens[j] == t.params.size();
+      if (ok && ParamLens[j] && !ParamTypes[j])
+        return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null ParamTypes row"));
+      for (uint32_t k = 0; ok && k < ParamLens[j]; k++) ok = uint8_t(ParamTypes[j][k]) == t.params[k];
+    }
+    if (!ok) {
+      row[kCallsFnEntry] = WB_CALL_SKIP | kFuncSigMismatch;
+      continue;
+    }
+    uint32_t frc = 0, fslots = 0;
+    for (uint8_t ty : t.results) {
+      frc += cells_of_value(ty);
+      fslots += ty == wb::V128 ? 2 : 1;
+    }
+    pc = std::max(pc, uint32_t(map.size()));
+    rc = std::max(rc, frc);
+    res_slots = std::max(res_slots, fslots);
+    row[kCallsFnEntry] = F.imported ? WB_CALL_SKIP : F.entry_pc;   // (an import: BatchRun refuses)
+    row[kCallsFnCells] = uint32_t(map.size());
+    row[kCallsFnFunc] = uint32_t(f);
+    row[kCallsFnImport] = F.imported ? 1u : 0u;
+    row[kCallsFnMap] = uint32_t(maps.size());   // (relative; the table's length is added below)
+    maps.insert(maps.end(), map.begin(), map.end());
+  }
+  for (uint32_t j = 0; j < NumFuncs; j++) tab[size_t(j) * kCallsFnWords + kCallsFnMap] += uint32_t(tab.size());
+  tab.insert(tab.end(), maps.begin(), maps.end());
+  if (widest && !Slots) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null Slots"));
+  if (Stride < widest) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Stride is smaller than the widest row"));
+  if ((uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Slots is not 8-byte aligned"));
+  if ((uintptr_t(FuncOf) & 3u)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: FuncOf is not 4-byte aligned"));
+  if (widest && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Stride out of range"));
+  if (!device_rows_ok(C, FuncOf, 4, 4, "BatchSetCallsDevice") ||
+      !device_rows_ok(C, Slots, widest * 8, Stride * 8, "BatchSetCallsDevice"))
+    return R(kRuntimeError);
+  // the spare buffers the kernel writes; the result rows change size only on success
+  const uint32_t pcs = pc ? pc : 1;
+  const size_t pn = size_t(C->n) * pcs, rn = size_t(C->n) * (rc ? rc : 1);
+  WasmEdge_BatchContext::DevBuf<uint32_t> results;
+  if (!sized(C->params_spare, pn) || !sized(C->calls_spare, size_t(C->n) * 2) || !sized(C->call_fn_spare, C->n) ||
+      !sized(C->calls_sum, 1) || ((C->results.n != rn || !C->results.ptr) && !results.alloc(rn))) {
+    (void)hipGetLastError();
+    return R(C->fail(kRuntimeError, "device allocation failed"));
+  }
+  if (!upload_map(C, C->calls_tab, C->calls_tab_h, tab)) return R(kRuntimeError);
+  CallsPackParams p{};
+  p.func_of = FuncOf;
+  p.slots = Slots;
+  p.table = C->calls_tab.ptr;
+  p.calls = C->calls_spare.ptr;
+  p.params = C->params_spare.ptr;
+  p.call_fn = C->call_fn_spare.ptr;
+  p.sum = C->calls_sum.ptr;
+  p.stride = Stride;
+  p.n = C->n;
+  p.pc = pcs;
+  p.nfuncs = NumFuncs;
+  if (!C->hip_ok(hipMemsetAsync(C->calls_sum.ptr, 0, sizeof(CallsSummary), C->stream), "call summary") ||
+      !C->hip_ok(wb_launch_calls_pack(&p, C->stream), "calls pack") ||
+      !C->hip_ok(hipMemcpyAsync(&C->calls_sum_h, C->calls_sum.ptr, sizeof(CallsSummary), hipMemcpyDeviceToHost,
+                                C->stream), "call summary") ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "calls pack"))
+    return R(kRuntimeError);
+  if (C->calls_sum_h.bad)
+    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: FuncOf[" + std::to_string(~C->calls_sum_h.bad) +
+                                       "] names no function"));
+  swap_bufs(C->params, C->params_spare);
+  swap_bufs(C->calls, C->calls_spare);
+  swap_bufs(C->call_fn, C->call_fn_spare);
+  if (results.ptr) swap_bufs(C->results, results);
+  // the vector's and the cells' order-independent sum: equal for equal device vectors, not
+  // the value BatchSetCalls gives the same vector
+  C->args_fp = args_fp_mix(~uint64_t(1), 0xC0C0C0C0u) + C->calls_sum_h.fp;
+  C->func = -1;
+  C->param_cells = pcs;
+  C->result_cells = rc;
+  C->result_types.clear();
+  C->call_host_ok = false;   // (call_func / call_status: fetched on first need, calls_mirror)
+  C->call_dev_ok = true;
+  C->calls_res_slots = res_slots;
+  C->calls_xref = false;
+  C->calls_import = C->calls_sum_h.imported != 0;
+  C->calls_on = true;
+  C->restage = false;
+  C->end_invocation();
+  return R(0);
+}
+
+WasmEdge_Result WasmEdge_BatchCallsResultsDevice(WasmEdge_BatchContext *C, uint64_t *Slots, const uint32_t Width,
+                                                 const uint64_t Stride, uint32_t *ReturnLens, uint8_t *PerInstance,
+                                                 uint64_t *InstrCounts) {
+  if (!C) return R(kWrongVMWorkflow);
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchResults"));
+  if (!C->calls_on)
+    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: no per-instance calls are staged: use BatchResultsDevice"));
+  if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
+  if (Slots && Stride < Width) return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Stride is smaller than Width"));
+  if (Slots && Width < C->calls_res_slots)
+    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Width is smaller than the widest result row (" +
+                                       std::to_string(C->calls_res_slots) + " slots)"));
+  if ((uintptr_t(Slots) & 7u) || (uintptr_t(InstrCounts) & 7u) || (uintptr_t(ReturnLens) & 3u))
+    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: a misaligned pointer"));
+  if (Slots && Width && Stride > (~0ull >> 4))
+    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Stride out of range"));
+  if (Slots && C->calls_xref)
+    return R(C->fail(kRuntimeError, "BatchCallsResultsDevice: externref values are interned on the host: use BatchResults"));
+  DevScope dev(C);
+  const uint32_t width = Slots ? Width : 0;
+  if (!device_rows_ok(C, Slots, uint64_t(width) * 8, Stride * 8, "BatchCallsResultsDevice") ||
+      !device_rows_ok(C, ReturnLens, 4, 4, "BatchCallsResultsDevice") ||
+      !device_rows_ok(C, PerInstance, 1, 1, "BatchCallsResultsDevice") ||
+      !device_rows_ok(C, InstrCounts, 8, 8, "BatchCallsResultsDevice"))
+    return R(kRuntimeError);
+  // (every launch and host-import round of the run has ended: launch_once waits for its
+  // kernel, a restore of a suspended invocation for its own)
+  if (width || ReturnLens) {
+    // each instance's function on the device: there already after SetCallsDevice, uploaded
+    // after BatchSetCalls or a restore that rewrote call_func on the host
+    if (!C->call_dev_ok) {
+      if (!sized(C->call_fn, C->n)) {
+        (void)hipGetLastError();
+        return R(C->fail(kRuntimeError, "device allocation failed"));
+      }
+      if (!C->hip_ok(hipMemcpyAsync(C->call_fn.ptr, C->call_func.data(), size_t(C->n) * 4, hipMemcpyHostToDevice,
+                                    C->stream), "call vector upload"))
+        return R(kRuntimeError);
+      C->call_dev_ok = true;
+    }
+    // the module's result table (calls_io.h), built and uploaded once
+    if (C->res_tab_h.empty()) {
+      const wb::Program &P = C->prog;
+      std::vector<uint32_t> tab(P.funcs.size() * kCallsResWords, 0), maps;
+      for (size_t f = 0; f < P.funcs.size(); f++) {
+        const std::vector<uint8_t> &types = P.types[P.funcs[f].type].results;
+        uint32_t cell = 0;
+        tab[f * kCallsResWords + kCallsResLen] = uint32_t(types.size());
+        tab[f * kCallsResWords + kCallsResMap] = uint32_t(tab.size() + maps.size());
+        for (uint8_t ty : types) {
+          const uint32_t nc = cells_of_value(ty);
+          for (uint32_t q = 0; q < nc; q++) maps.push_back(cell++);
+          if (nc == 1) maps.push_back(kArgsNoCell);
+        }
+        tab[f * kCallsResWords + kCallsResSlots] = uint32_t(tab.size() + maps.size() - tab[f * kCallsResWords + kCallsResMap]) / 2;
+      }
+      tab.insert(tab.end(), maps.begin(), maps.end());
+      tab.push_back(0);   // (never empty)
+      if (!upload_map(C, C->res_tab, C->res_tab_h, tab)) return R(kRuntimeError);
+    }
+    CallsUnpackParams p{};
+    p.results = C->results.ptr;
+    p.status = C->status.ptr;
+    p.call_fn = C->call_fn.ptr;
+    p.table = C->res_tab.ptr;
+    p.slots = Slots;
+    p.lens = ReturnLens;
+    p.stride = Stride;
+    p.n = C->n;
+    p.cells = C->result_cells;
+    p.width = width;
+    if (!C->hip_ok(wb_launch_calls_unpack(&p, C->stream), "results unpack")) return R(kRuntimeError);
   }
   if (PerInstance && !C->hip_ok(hipMemcpyAsync(PerInstance, C->status.ptr, C->n, hipMemcpyDeviceToDevice, C->stream), "status"))
     return R(kRuntimeError);

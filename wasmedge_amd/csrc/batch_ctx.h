@@ -17,6 +17,7 @@
 #include "tc.h"
 #include "kparams.h"
 #include "mem_layout.h"
+#include "calls_io.h"
 #include "wasi_impl.h"
 
 namespace wbh {
@@ -228,6 +229,55 @@ struct WasmEdge_BatchContext {
   std::vector<uint32_t> pack_map_h, unpack_map_h;
   DevBuf<uint64_t> args_sum;
   uint64_t args_sum_h = 0;
+  // device-resident per-instance calls (WasmEdge_BatchSetCallsDevice / CallsResultsDevice,
+  // calls_io.h). call_fn is call_func on the device; one flag per side says which copy is
+  // current (calls_mirror / CallsResultsDevice bring the other up to date on first need).
+  // The pack kernel writes the spare buffers, swapped in when the call succeeds, so a refused
+  // FuncOf leaves the live staging runnable. calls_tab: the per-name table of the last
+  // SetCallsDevice, res_tab: the per-function result table of the module (built once), each
+  // with the host copy it was uploaded from. calls_res_slots / calls_xref: the widest result
+  // row of the staging's functions in slots, and whether one returns an externref.
+  DevBuf<int32_t> call_fn, call_fn_spare;
+  DevBuf<uint32_t> calls_spare, params_spare;
+  bool call_host_ok = true, call_dev_ok = false;
+  DevBuf<uint32_t> calls_tab, res_tab;
+  std::vector<uint32_t> calls_tab_h, res_tab_h;
+  DevBuf<CallsSummary> calls_sum;
+  CallsSummary calls_sum_h{};
+  uint32_t calls_res_slots = 0;
+  bool calls_xref = false;
+  // call_func / call_status after a SetCallsDevice, which read back only the summary: fetched
+  // from call_fn and the call table's entries (the staging call synchronised its stream)
+  bool calls_mirror() {
+    if (call_host_ok) return true;
+    // (the whole [n][2] table in one copy: a strided copy of the entries alone took 6 ms at
+    // 65,536 instances)
+    std::vector<uint32_t> tab(size_t(n) * 2);
+    call_func.assign(n, -1);
+    call_status.assign(n, 0);
+    if (!hip_ok(hipMemcpy(call_func.data(), call_fn.ptr, size_t(n) * 4, hipMemcpyDeviceToHost), "call vector") ||
+        !hip_ok(hipMemcpy(tab.data(), calls.ptr, tab.size() * 4, hipMemcpyDeviceToHost), "call vector"))
+      return false;
+    for (uint32_t i = 0; i < n; i++) call_status[i] = tab[2 * size_t(i)] >= WB_CALL_SKIP ? uint8_t(tab[2 * size_t(i)]) : 0;
+    call_host_ok = true;
+    return true;
+  }
+  // calls_res_slots / calls_xref from call_func (the host copy is current)
+  void calls_shape() {
+    calls_res_slots = 0;
+    calls_xref = false;
+    std::vector<uint8_t> seen(prog.funcs.size(), 0);
+    for (int32_t f : call_func) {
+      if (f < 0 || seen[f]) continue;
+      seen[f] = 1;
+      uint32_t slots = 0;
+      for (uint8_t ty : prog.types[prog.funcs[f].type].results) {
+        slots += ty == wb::V128 ? 2 : 1;
+        calls_xref |= ty == wb::EXTERNREF;
+      }
+      if (slots > calls_res_slots) calls_res_slots = slots;
+    }
+  }
   // resumable runs (conf.Resumable; DESIGN.md "Resumable runs"): the invocation BatchResume
   // continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
   // Run / SnapshotRestore --, its entry pc, the cumulative step limit of the call in

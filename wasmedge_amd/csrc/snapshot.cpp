@@ -152,6 +152,7 @@ bool capture_invocation(Ctx *C, Snap *S) {
       !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot") ||
       !C->hip_ok(hipMemcpy(hc.data(), C->hcall.ptr, size_t(C->n) * 4, hipMemcpyDeviceToHost), "snapshot"))
     return false;
+  if (C->calls_on && !C->calls_mirror()) return false;   // (a device-staged vector: fetched now)
   S->susp_h.assign(C->n, 0);
   S->suspended = 0;
   for (uint32_t i = 0; i < C->n; i++)
@@ -445,6 +446,10 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
         C->call_status[i] = S->call_status[s];
       }
     }
+    // (calls_io: the host copy is the current one, CallsResultsDevice uploads it on first need)
+    C->call_host_ok = true;
+    C->call_dev_ok = false;
+    C->calls_shape();
     C->inv_pc = S->inv_pc;
     C->inv_live = true;
     C->ran = true;
