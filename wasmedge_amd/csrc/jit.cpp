@@ -2373,7 +2373,9 @@ bool written_exact(const DInstr &I, std::vector<uint32_t> *out) {
 // reference's x86 build produces (Em::nan_fix: a compare and a branch per result). That
 // only matters where the payload can be observed: stored, returned, kept in a global,
 // passed to a call, or read as bits by an op whose result can be. A float compare sees
-// every NaN alike. nan_observable() is a backward dataflow over the program's cells:
+// every NaN of its own width alike -- as long as no integer or bitwise op has made an
+// ordinary value of the payload on the way (the levels below).
+// nan_observable() is a backward dataflow over the program's cells:
 // obs(pc) = the cells whose bits may still reach such a sink after instruction pc; an
 // add/sub/mul whose result is in no obs(pc) needs no fix (C5: the Mandelbrot iteration's
 // z values only ever reach a compare). Unmodelled instructions make everything they name
@@ -2387,20 +2389,31 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
                                     std::vector<std::vector<uint64_t>> *live = nullptr) {
   const size_t n = P.code.size();
   const uint32_t nc = P.total_cells() + 8;   // (+8: 4-wide over-approximations stay in range)
-  const size_t W = (nc + 63) / 64;
+  const size_t W1 = (nc + 63) / 64;
+  // Three levels per cell. BITS: its bits may reach a sink. F32 / F64: it may reach a float
+  // compare or truncation that reads it as an f32 / as half of an f64 -- its value as that
+  // float matters, the payload of a NaN of that width does not. An add/sub/mul of width w
+  // needs its fix when its result is wanted at BITS or as the other width (the low word of an
+  // f64 NaN, read as an f32, is an ordinary number). Only float ops of the same width and
+  // plain moves hand a float level on to their sources; every other op (v128.and, an integer
+  // add, a shift, a bitmask, copysign's sign operand ...) turns payload bits into ordinary
+  // values, so its sources are wanted at BITS whenever its result is wanted at all.
+  enum { BITS = 0, F32 = 1, F64 = 2, LEVELS = 3 };
+  const size_t W = live ? W1 : LEVELS * W1;   // (plain liveness keeps the one level)
   typedef std::vector<uint64_t> Set;
   std::vector<Set> before(n + 1, Set(W, 0));
-  auto put = [&](Set &s, uint32_t c, uint32_t k) {
+  auto put = [&](Set &s, uint32_t c, uint32_t k, int lv = BITS) {
     for (uint32_t q = 0; q < k; q++)
-      if (c + q < nc) s[(c + q) >> 6] |= 1ull << ((c + q) & 63);
+      if (c + q < nc) s[lv * W1 + ((c + q) >> 6)] |= 1ull << ((c + q) & 63);
   };
   auto kill = [&](Set &s, uint32_t c, uint32_t k) {
-    for (uint32_t q = 0; q < k; q++)
-      if (c + q < nc) s[(c + q) >> 6] &= ~(1ull << ((c + q) & 63));
+    for (size_t lv = 0; lv * W1 < W; lv++)
+      for (uint32_t q = 0; q < k; q++)
+        if (c + q < nc) s[lv * W1 + ((c + q) >> 6)] &= ~(1ull << ((c + q) & 63));
   };
-  auto any = [&](const Set &s, uint32_t c, uint32_t k) {
+  auto any = [&](const Set &s, uint32_t c, uint32_t k, int lv = BITS) {
     for (uint32_t q = 0; q < k; q++)
-      if (c + q < nc && (s[(c + q) >> 6] >> ((c + q) & 63) & 1)) return true;
+      if (c + q < nc && (s[lv * W1 + ((c + q) >> 6)] >> ((c + q) & 63) & 1)) return true;
     return false;
   };
   Set all(W, ~0ull), globals(W, 0);
@@ -2421,47 +2434,60 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
       // names is observable
       uint32_t src[3][2] = {{0, 0}, {0, 0}, {0, 0}}, dst[2] = {0, 0};   // (cell, count)
       enum { PROP, HIDE, SINK, ALL, EXIT } kind = SINK;
+      // a PROP op's way with levels: a float op of one width, a move (its results are copies
+      // of source cells), or anything else; fl: the level a HIDE op reads its sources at
+      enum { C_BITS, C_F32, C_F64, C_MOVE } cls = C_BITS;
+      int fl = F32;
       auto bin = [&](uint32_t w, uint32_t rw) { src[0][0] = a; src[0][1] = w; src[1][0] = b; src[1][1] = w; dst[0] = c; dst[1] = rw; };
       auto un = [&](uint32_t w, uint32_t rw) { src[0][0] = a; src[0][1] = w; dst[0] = c; dst[1] = rw; };
       std::vector<uint32_t> wx;
       switch (op) {
         case OP_F32_ADD: case OP_F32_SUB: case OP_F32_MUL: case OP_F32_DIV: case OP_F32_MIN:
-        case OP_F32_MAX: case OP_F32_COPYSIGN: kind = PROP; bin(1, 1); break;
+        case OP_F32_MAX: case OP_F32_COPYSIGN: kind = PROP; cls = C_F32; bin(1, 1); break;
         case OP_F64_ADD: case OP_F64_SUB: case OP_F64_MUL: case OP_F64_DIV: case OP_F64_MIN:
-        case OP_F64_MAX: case OP_F64_COPYSIGN: kind = PROP; bin(2, 2); break;
+        case OP_F64_MAX: case OP_F64_COPYSIGN: kind = PROP; cls = C_F64; bin(2, 2); break;
         case OP_F32_ABS: case OP_F32_NEG: case OP_F32_CEIL: case OP_F32_FLOOR: case OP_F32_TRUNC:
-        case OP_F32_NEAREST: case OP_F32_SQRT: case OP_MOV32: kind = PROP; un(1, 1); break;
+        case OP_F32_NEAREST: case OP_F32_SQRT: kind = PROP; cls = C_F32; un(1, 1); break;
+        case OP_MOV32: kind = PROP; cls = C_MOVE; un(1, 1); break;
         case OP_F64_ABS: case OP_F64_NEG: case OP_F64_CEIL: case OP_F64_FLOOR: case OP_F64_TRUNC:
-        case OP_F64_NEAREST: case OP_F64_SQRT: case OP_MOV64: kind = PROP; un(2, 2); break;
+        case OP_F64_NEAREST: case OP_F64_SQRT: kind = PROP; cls = C_F64; un(2, 2); break;
+        case OP_MOV64: kind = PROP; cls = C_MOVE; un(2, 2); break;
+        // (a conversion between the widths: its source is wanted at BITS, which is more than
+        // needed and costs nothing -- the compiled runs do not emit these ops)
         case OP_F32_DEMOTE_F64: kind = PROP; un(2, 1); break;
         case OP_F64_PROMOTE_F32: kind = PROP; un(1, 2); break;
-        case OP_MOV128: case OP_V_NOT: case OP_V_F32X4_ABS: case OP_V_F32X4_NEG: case OP_V_F32X4_SQRT:
-        case OP_V_F64X2_ABS: case OP_V_F64X2_NEG: case OP_V_F64X2_SQRT: kind = PROP; un(4, 4); break;
+        case OP_MOV128: kind = PROP; cls = C_MOVE; un(4, 4); break;
+        case OP_V_NOT: kind = PROP; un(4, 4); break;
+        case OP_V_F32X4_ABS: case OP_V_F32X4_NEG: case OP_V_F32X4_SQRT: kind = PROP; cls = C_F32; un(4, 4); break;
+        case OP_V_F64X2_ABS: case OP_V_F64X2_NEG: case OP_V_F64X2_SQRT: kind = PROP; cls = C_F64; un(4, 4); break;
         case OP_CONST32: kind = PROP; dst[0] = c; dst[1] = 1; break;
         case OP_CONST64: kind = PROP; dst[0] = c; dst[1] = 2; break;
         case OP_CONST128: kind = PROP; dst[0] = c; dst[1] = 4; break;
-        case OP_V_I32X4_SPLAT: case OP_V_F32X4_SPLAT: kind = PROP; un(1, 4); break;
-        case OP_V_I64X2_SPLAT: case OP_V_F64X2_SPLAT: kind = PROP; un(2, 4); break;
+        case OP_V_I32X4_SPLAT: case OP_V_F32X4_SPLAT: kind = PROP; cls = C_MOVE; un(1, 4); break;
+        case OP_V_I64X2_SPLAT: case OP_V_F64X2_SPLAT: kind = PROP; cls = C_MOVE; un(2, 4); break;
         case OP_V_AND: case OP_V_OR: case OP_V_XOR: case OP_V_ANDNOT: case OP_V_I32X4_ADD:
         case OP_V_I32X4_SUB: case OP_V_I32X4_MUL: case OP_V_I64X2_ADD: case OP_V_I64X2_SUB:
+          kind = PROP; bin(4, 4); break;
         case OP_V_F32X4_ADD: case OP_V_F32X4_SUB: case OP_V_F32X4_MUL: case OP_V_F32X4_DIV:
         case OP_V_F32X4_MIN: case OP_V_F32X4_MAX: case OP_V_F32X4_PMIN: case OP_V_F32X4_PMAX:
+          kind = PROP; cls = C_F32; bin(4, 4); break;
         case OP_V_F64X2_ADD: case OP_V_F64X2_SUB: case OP_V_F64X2_MUL: case OP_V_F64X2_DIV:
         case OP_V_F64X2_MIN: case OP_V_F64X2_MAX: case OP_V_F64X2_PMIN: case OP_V_F64X2_PMAX:
-          kind = PROP; bin(4, 4); break;
-        case OP_V_EXTRACT32: kind = PROP; un(4, 1); break;
-        case OP_V_EXTRACT64: kind = PROP; un(4, 2); break;
-        case OP_V_REPLACE32: kind = PROP; bin(4, 4); src[1][1] = 1; break;
-        case OP_V_REPLACE64: kind = PROP; bin(4, 4); src[1][1] = 2; break;
+          kind = PROP; cls = C_F64; bin(4, 4); break;
+        case OP_V_EXTRACT32: kind = PROP; cls = C_MOVE; un(4, 1); break;
+        case OP_V_EXTRACT64: kind = PROP; cls = C_MOVE; un(4, 2); break;
+        case OP_V_REPLACE32: kind = PROP; cls = C_MOVE; bin(4, 4); src[1][1] = 1; break;
+        case OP_V_REPLACE64: kind = PROP; cls = C_MOVE; bin(4, 4); src[1][1] = 2; break;
         case OP_V_ANY_TRUE: kind = PROP; un(4, 1); break;
         case OP_F32_EQ: case OP_F32_NE: case OP_F32_LT: case OP_F32_GT: case OP_F32_LE: case OP_F32_GE:
-          kind = HIDE; dst[0] = c; dst[1] = 1; break;
+          kind = HIDE; fl = F32; bin(1, 1); break;
         case OP_F64_EQ: case OP_F64_NE: case OP_F64_LT: case OP_F64_GT: case OP_F64_LE: case OP_F64_GE:
-          kind = HIDE; dst[0] = c; dst[1] = 1; break;
+          kind = HIDE; fl = F64; bin(2, 1); break;
         case OP_V_F32X4_EQ: case OP_V_F32X4_NE: case OP_V_F32X4_LT: case OP_V_F32X4_GT:
-        case OP_V_F32X4_LE: case OP_V_F32X4_GE: case OP_V_F64X2_EQ: case OP_V_F64X2_NE:
+        case OP_V_F32X4_LE: case OP_V_F32X4_GE: kind = HIDE; fl = F32; bin(4, 4); break;
+        case OP_V_F64X2_EQ: case OP_V_F64X2_NE:
         case OP_V_F64X2_LT: case OP_V_F64X2_GT: case OP_V_F64X2_LE: case OP_V_F64X2_GE:
-          kind = HIDE; dst[0] = c; dst[1] = 4; break;
+          kind = HIDE; fl = F64; bin(4, 4); break;
         case OP_I64_ADD: case OP_I64_SUB: case OP_I64_MUL: case OP_I64_AND: case OP_I64_OR:
         case OP_I64_XOR: case OP_I64_SHL: case OP_I64_SHR_S: case OP_I64_SHR_U: case OP_I64_ROTL:
         case OP_I64_ROTR: kind = PROP; bin(2, 2); break;
@@ -2482,7 +2508,7 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
         case OP_F64_CONVERT_I64_S: case OP_F64_CONVERT_I64_U: kind = PROP; un(2, 2); break;
         case OP_SELECT32: case OP_SELECT64: case OP_SELECT128: {
           const uint32_t w = op == OP_SELECT32 ? 1 : op == OP_SELECT64 ? 2 : 4;
-          kind = PROP; bin(w, w); src[2][0] = d; src[2][1] = 1; break;
+          kind = PROP; cls = C_MOVE; bin(w, w); src[2][0] = d; src[2][1] = 1; break;
         }
         case OP_V_I8X16_EQ: case OP_V_I8X16_NE: case OP_V_I16X8_EQ: case OP_V_I16X8_NE:
         case OP_V_I32X4_EQ: case OP_V_I32X4_NE: case OP_V_I32X4_LT_S: case OP_V_I32X4_LT_U:
@@ -2495,14 +2521,14 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
         case OP_V_I64X2_BITMASK: case OP_V_I8X16_ALL_TRUE: case OP_V_I16X8_ALL_TRUE:
         case OP_V_I32X4_ALL_TRUE: case OP_V_I64X2_ALL_TRUE: kind = PROP; un(4, 1); break;
         // float -> int: a NaN traps or saturates whatever its payload
-        case OP_I32_TRUNC_F32_S: case OP_I32_TRUNC_F32_U: case OP_I32_TRUNC_F64_S:
-        case OP_I32_TRUNC_F64_U: case OP_I32_TRUNC_SAT_F32_S: case OP_I32_TRUNC_SAT_F32_U:
-        case OP_I32_TRUNC_SAT_F64_S: case OP_I32_TRUNC_SAT_F64_U:
-          kind = HIDE; dst[0] = c; dst[1] = 1; break;
-        case OP_I64_TRUNC_F32_S: case OP_I64_TRUNC_F32_U: case OP_I64_TRUNC_F64_S:
-        case OP_I64_TRUNC_F64_U: case OP_I64_TRUNC_SAT_F32_S: case OP_I64_TRUNC_SAT_F32_U:
-        case OP_I64_TRUNC_SAT_F64_S: case OP_I64_TRUNC_SAT_F64_U:
-          kind = HIDE; dst[0] = c; dst[1] = 2; break;
+        case OP_I32_TRUNC_F32_S: case OP_I32_TRUNC_F32_U: case OP_I32_TRUNC_SAT_F32_S:
+        case OP_I32_TRUNC_SAT_F32_U: kind = HIDE; fl = F32; un(1, 1); break;
+        case OP_I32_TRUNC_F64_S: case OP_I32_TRUNC_F64_U: case OP_I32_TRUNC_SAT_F64_S:
+        case OP_I32_TRUNC_SAT_F64_U: kind = HIDE; fl = F64; un(2, 1); break;
+        case OP_I64_TRUNC_F32_S: case OP_I64_TRUNC_F32_U: case OP_I64_TRUNC_SAT_F32_S:
+        case OP_I64_TRUNC_SAT_F32_U: kind = HIDE; fl = F32; un(1, 2); break;
+        case OP_I64_TRUNC_F64_S: case OP_I64_TRUNC_F64_U: case OP_I64_TRUNC_SAT_F64_S:
+        case OP_I64_TRUNC_SAT_F64_U: kind = HIDE; fl = F64; un(2, 2); break;
         case OP_NOP_CNT: kind = PROP; break;
         case OP_ZERO_LOCALS: kind = PROP; dst[0] = a; dst[1] = b; break;
         case OP_RET: case OP_UNREACHABLE: kind = EXIT; break;
@@ -2535,12 +2561,37 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
         }
         s = after;
         if (kind == PROP || kind == HIDE) {
-          const bool used = any(after, dst[0], dst[1]);
-          if (dst[1]) res[pc] = used ? 1 : 0;
+          const bool ub = any(after, dst[0], dst[1]);
+          const bool u32 = !live && any(after, dst[0], dst[1], F32), u64 = !live && any(after, dst[0], dst[1], F64);
+          const bool used = ub || u32 || u64;
+          // (a float op's flag: whether a NaN it makes needs the reference's payload)
+          if (dst[1]) res[pc] = (cls == C_F32 ? ub || u64 : cls == C_F64 ? ub || u32 : used) ? 1 : 0;
           kill(s, dst[0], dst[1]);
-          if (kind == PROP && (used || live))
+          if (live) {
+            if (kind == PROP)
+              for (auto &x : src) put(s, x[0], x[1]);
+            if (kind == HIDE) { put(s, a, 4); put(s, b, 4); }
+          } else if (kind == HIDE) {   // (always: a truncation's trap depends on its operand)
+            for (auto &x : src) put(s, x[0], x[1], fl);
+          } else if (used && cls == C_MOVE) {
+            for (int k = 0; k < 2; k++) {
+              if (ub) put(s, src[k][0], src[k][1]);
+              if (u32) put(s, src[k][0], src[k][1], F32);
+              if (u64) put(s, src[k][0], src[k][1], F64);
+            }
+            put(s, src[2][0], src[2][1]);   // (a select's condition)
+          } else if (used && cls != C_BITS) {
+            const int own = cls == C_F32 ? F32 : F64;
+            const bool as_float = cls == C_F32 ? u32 : u64, as_bits = cls == C_F32 ? ub || u64 : ub || u32;
+            // (copysign takes its second operand's sign bit, a NaN's included)
+            const bool sign = op == OP_F32_COPYSIGN || op == OP_F64_COPYSIGN;
+            for (int k = 0; k < 2; k++) {
+              if (as_float && !(sign && k == 1)) put(s, src[k][0], src[k][1], own);
+              if (as_bits || (sign && k == 1)) put(s, src[k][0], src[k][1]);
+            }
+          } else if (used) {
             for (auto &x : src) put(s, x[0], x[1]);
-          if (kind == HIDE && live) { put(s, a, 4); put(s, b, 4); }
+          }
         } else if (is_store_op(op)) {   // the address and the stored bits
           put(s, a, 1);
           put(s, b, std::max(1u, mem_bytes(op) / 4));
@@ -2567,7 +2618,7 @@ std::vector<uint8_t> nan_observable(const Program &P, const JitKnobs &kn,
       }
     }
   }
-  if (live) *live = before;
+  if (live) *live = before;   // (W == W1: the one level)
   // (debugging aid: WB_NANOBS_LIST=<file>, JitKnobs::nanobs_list, writes per pc the flag and the cells observable
   // before it)
   if (const char *lst = kn.nanobs_list)
