@@ -772,7 +772,42 @@ WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Off
  * with a message when it cannot, all state unchanged). Reset, SetArgs, SetCalls, Run and a
  * restore of a snapshot without an invocation end it as usual. The staged arguments are not
  * captured: when the restore maps instances (SrcOf) or the context staged other arguments
- * since the capture, a BatchRun needs SetArgs / SetCalls first (WrongVMWorkflow otherwise). */
+ * since the capture, a BatchRun needs SetArgs / SetCalls first (WrongVMWorkflow otherwise).
+ *
+ * SnapshotRestoreSelected: a restore that leaves some instances alone -- "reset the finished
+ * environments, step the others". SrcOf is [NumInstances] and must not be NULL (for "every
+ * instance from itself" there is SnapshotRestore). SrcOf[i] == WASMEDGE_BATCH_SNAPSHOT_KEEP:
+ * instance i keeps everything a snapshot would have overwritten -- memory 0 with its size and
+ * write mark, memories 1..7 and their sizes, its globals, its tables with their sizes and
+ * dropped element segments, its dropped data segments, its instantiation status, its gas total
+ * and its built-in WASI state. Any other entry means what it means for SnapshotRestore.
+ * *NumRestored (may be NULL) = the instances that were not kept. (SnapshotRestore keeps its
+ * contract to the letter: 0xFFFFFFFF there is an instance past NumInstances, 0x04.) For the
+ * call as a whole it is a SnapshotRestore: the last run's results are gone, a live suspended
+ * invocation of the context ends (kept instances are written "not parked" with the others, so
+ * the next BatchRun starts them cleanly), staged arguments stay, the layout neither changes
+ * nor matters. Failures, with all state unchanged: WrongVMWorkflow (0x04) for a NULL context,
+ * snapshot or map, a snapshot of another context, an entry that is neither KEEP nor below
+ * NumInstances, and for a map with a KEEP together with a snapshot that holds an invocation
+ * (SnapshotCreateSuspended): which invocation a kept instance would then belong to is not
+ * defined here. A map without KEEP on such a snapshot behaves exactly as SnapshotRestore.
+ * RuntimeError (0x02) with a message when a kept instance holds pages past the reserved layout
+ * and the layout cannot grow to take them (as SnapshotCreate; the context stays usable), and
+ * on a multi-device context for a map with an entry that is neither KEEP nor i (nothing may
+ * cross a device; a map of KEEP and i entries is legal there; the pool-row step runs on every
+ * shard before the first is restored, while a device error in the middle may leave earlier
+ * shards restored, as with SnapshotRestore).
+ *
+ * SnapshotRestoreSelectedDevice: the same from a map in device memory (a selection computed
+ * on the device from statuses or results that never left it). The caller synchronises
+ * whatever produced SrcOfDevice. A buffer this HIP runtime allocated must lie on the
+ * context's device and hold NumInstances words, else RuntimeError (0x02); so is any call on a
+ * multi-device context. The map is validated and the restore planned by a kernel; the call
+ * synchronises once before the restore's kernels, to read that kernel's summary -- an invalid
+ * map (0x04) leaves the context as it was --, and with KernelSeconds NULL does not wait after
+ * them. For a snapshot that holds WASI state or an invocation the map is read back once
+ * (NumInstances * 4 bytes) and the call is SnapshotRestoreSelected. */
+#define WASMEDGE_BATCH_SNAPSHOT_KEEP 0xFFFFFFFFu
 typedef struct WasmEdge_BatchSnapshot WasmEdge_BatchSnapshot;
 WASMEDGE_BATCH_API WasmEdge_BatchSnapshot *WasmEdge_BatchSnapshotCreate(WasmEdge_BatchContext *Cxt,
                                                                         WasmEdge_Result *Res);
@@ -782,6 +817,13 @@ WASMEDGE_BATCH_API uint32_t WasmEdge_BatchSnapshotGetSuspendedCount(const WasmEd
 WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *Cxt, const WasmEdge_BatchSnapshot *Snap,
                               const uint32_t *SrcOf, double *KernelSeconds);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSnapshotRestoreSelected(WasmEdge_BatchContext *Cxt, const WasmEdge_BatchSnapshot *Snap,
+                                      const uint32_t *SrcOf, uint32_t *NumRestored, double *KernelSeconds);
+WASMEDGE_BATCH_API WasmEdge_Result
+WasmEdge_BatchSnapshotRestoreSelectedDevice(WasmEdge_BatchContext *Cxt, const WasmEdge_BatchSnapshot *Snap,
+                                            const uint32_t *SrcOfDevice, uint32_t *NumRestored,
+                                            double *KernelSeconds);
 WASMEDGE_BATCH_API uint64_t WasmEdge_BatchSnapshotGetBytes(const WasmEdge_BatchSnapshot *Snap);
 WASMEDGE_BATCH_API void WasmEdge_BatchSnapshotDelete(WasmEdge_BatchSnapshot *Snap);
 /* Exported tables and globals of one instance, by export name (the batched form of

@@ -14,6 +14,16 @@ marks), granules 4 and 128 bytes.
 
     python tools/snapshot_probe.py [--instances 65536] [--shapes c2,c3_4k,c3_1m]
                                    [--out profiles/snapshot_probe.json]
+
+--select measures the selective restore instead (WasmEdge_BatchSnapshotRestoreSelected /
+RestoreSelectedDevice, DESIGN.md "Selective restore") on c2 and c3_4k, same method: the
+identity restore(snap) as the yardstick, then `none`, `all`, whole waves kept for half of the
+waves, `alternate`, 10% of the lanes restored from themselves and the same 10% from random
+sources, each with the bytes of memory 0 its plan reads and writes; and, on c2, the wall clock
+of the 10% restore from a host map against the same map already on the device. One JSON line,
+written to profiles/snapshot_select_<first 8 digits of the source hash>.json.
+
+    python tools/snapshot_probe.py --select [--instances 65536]
 """
 import argparse
 import json
@@ -55,6 +65,105 @@ def alternate(fns, reps=7, warm=2):
     return {k: stats(v) for k, v in out.items()}
 
 
+KEEP = batch.KEEP
+
+
+def select_maps(n):
+    """the measured maps, uint32 [n] with KEEP for a kept lane"""
+    ids = np.arange(n, dtype=np.uint32)
+    rng = np.random.RandomState(9)
+    tenth = rng.rand(n) < 0.1
+    return {"none": ids.copy(), "all": np.full(n, KEEP, np.uint32),
+            "half_waves": np.where((ids >> 6) & 1, np.uint32(KEEP), ids),
+            "alternate": np.where(ids & 1, np.uint32(KEEP), ids),
+            "tenth_self": np.where(tenth, ids, np.uint32(KEEP)),
+            "tenth_random": np.where(tenth, rng.randint(0, n, n).astype(np.uint32), np.uint32(KEEP))}
+
+
+def implied_bytes(m, wave_bytes, granule):
+    """Bytes of memory 0 the plan of map m reads and writes, wave by wave (snapshot_plan.h
+    plan_restore and the kernels' paths). wave_bytes: what a wave's marks bound, the same for
+    every wave of these shapes and the same now as at the capture, taken from the snapshot's
+    size. A wave without kept lanes reads and writes its rows once. A mixed wave whose
+    restored lanes share a source wave reads that wave's rows whole, otherwise each restored
+    lane's own; it reads the live tiles and writes them whole where a 16-byte piece spans
+    lanes (granules below 16 bytes), and writes the restored lanes' pieces alone otherwise."""
+    n = len(m)
+    rd = wr = 0
+    for w in range(0, n, 64):
+        lanes = m[w:w + 64]
+        rest = lanes[lanes != KEEP]
+        if len(rest) == 0:
+            continue
+        share = len(rest) / len(lanes)
+        if len(rest) == len(lanes):
+            rd += wave_bytes
+            wr += wave_bytes
+            continue
+        one = len(set(int(x) >> 6 for x in rest)) == 1
+        rd += wave_bytes if one else wave_bytes * share
+        if granule < 16:
+            rd += wave_bytes
+            wr += wave_bytes
+        else:
+            wr += wave_bytes * share
+    return int(rd), int(wr)
+
+
+def select_probe(n):
+    import torch
+    sys.path.insert(0, os.path.join(ROOT, "wasmedge_amd", "csrc"))
+    import srchash
+    maps = select_maps(n)
+    ids = np.arange(n, dtype=np.int64)
+    rows = []
+    plan = None
+    for shape in ("c2", "c3_4k"):
+        make, func, build, kw = SHAPES[shape]
+        wasm = make()
+        for granule in (4, 128):
+            ctx = batch.BatchContext(wasm, n, device=0, memory_granule=granule, **kw)
+            _, st, _ = ctx.execute(func, batch.make_values(build(ids), [I32, I32]), 1)
+            assert not st.any()
+            snap = ctx.snapshot()
+            nwaves = (n + 63) // 64
+            wave_bytes = snap.nbytes // nwaves   # (memory 0 beside the small whole buffers: an upper bound)
+            tens = {k: torch.from_numpy(v.view(np.int32)).to("cuda:0") for k, v in maps.items()}
+            fns = {"identity": lambda: ctx.restore(snap)}
+            for k, v in maps.items():
+                fns[k] = lambda v=v: ctx.restore_selected(snap, v.view(np.int32))[0]
+            r = alternate(fns)
+            row = {"shape": shape, "granule": granule, "instances": n, "snapshot_bytes": snap.nbytes,
+                   "identity": r["identity"], "maps": {}}
+            for k, v in maps.items():
+                rd, wr = implied_bytes(v, wave_bytes, granule)
+                row["maps"][k] = dict(r[k], read_bytes=rd, written_bytes=wr,
+                                      Bps=(rd + wr) / r[k]["median_s"] if rd + wr else 0.0)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+            if shape == "c2" and granule == 4:
+                # the plan: wall clock around the call (it ends in a synchronise), the host map
+                # against the same map on the device, its producer long finished
+                def wall(f):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    f()
+                    return time.perf_counter() - t0
+
+                host = maps["tenth_random"].view(np.int32)
+                plan = alternate({
+                    "host_map": lambda: wall(lambda: ctx.restore_selected(snap, host)),
+                    "device_map": lambda: wall(lambda: ctx.restore_tensor(snap, tens["tenth_random"]))})
+                plan = {"shape": shape, "granule": granule, "map": "tenth_random", "wall_clock": plan}
+                print(json.dumps(plan), flush=True)
+            snap.close()
+            ctx.close()
+    out = os.path.join(ROOT, "profiles", "snapshot_select_%s.json" % srchash.source_hash()[:8])
+    with open(out, "w") as fo:
+        fo.write(json.dumps({"select": rows, "plan": plan, "source_hash": srchash.source_hash()}) + "\n")
+    print("wrote " + out)
+
+
 def main():
     import torch
     torch.zeros(1, device="cuda:0")   # (torch's HIP runtime finds its device first)
@@ -62,7 +171,11 @@ def main():
     ap.add_argument("--instances", type=int, default=65536)
     ap.add_argument("--shapes", default="c2,c3_4k,c3_1m")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "snapshot_probe.json"))
+    ap.add_argument("--select", action="store_true", help="the selective restore (see above)")
     args = ap.parse_args()
+    if args.select:
+        select_probe(args.instances)
+        return
     n = args.instances
     ids = np.arange(n, dtype=np.int64)
     rng = np.random.RandomState(3)

@@ -31,6 +31,7 @@ STATUS_NAMES = {0x00: "ok", 0x07: "interrupted", 0x84: "integer divide by zero",
 
 ALL_INSTANCES = 0xFFFFFFFF
 NO_CALL = 0xFFFFFFFF    # WASMEDGE_BATCH_NO_CALL: the instance sits a set_calls run out
+KEEP = 0xFFFFFFFF       # WASMEDGE_BATCH_SNAPSHOT_KEEP: restore_selected leaves the instance alone
 REF_NULL = 0xFFFFFFFF   # null funcref / externref on the device (32-bit references)
 
 
@@ -236,6 +237,9 @@ def lib():
         L.WasmEdge_BatchSnapshotGetSuspendedCount.argtypes = [vp]
         L.WasmEdge_BatchSnapshotRestore.restype = _Result
         L.WasmEdge_BatchSnapshotRestore.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_double)]
+        for f in (L.WasmEdge_BatchSnapshotRestoreSelected, L.WasmEdge_BatchSnapshotRestoreSelectedDevice):
+            f.restype = _Result
+            f.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)]
         L.WasmEdge_BatchSnapshotGetBytes.restype = u64
         L.WasmEdge_BatchSnapshotGetBytes.argtypes = [vp]
         L.WasmEdge_BatchSnapshotDelete.restype = None
@@ -514,6 +518,53 @@ class BatchContext:
                                                         src.ctypes.data if src is not None else None,
                                                         ctypes.byref(t) if timed else None))
         return t.value
+
+    def restore_selected(self, snap, src_of, timed=True):
+        """restore() that leaves some instances alone (WasmEdge_BatchSnapshotRestoreSelected):
+        src_of[i] None or -1 keeps instance i as it is, any other entry restarts it from the
+        captured state of that instance. Returns (kernel seconds, instances restored)."""
+        if not isinstance(snap, Snapshot) or not snap._h:
+            raise ValueError("a Snapshot that is not closed is needed")
+        if src_of is None:
+            raise ValueError("src_of is needed (restore() restores every instance from itself)")
+        # an entry that does not fit 32 bits (or is negative and not -1) names no instance: it
+        # goes to the library as one that is neither KEEP nor below n, and comes back as 0x04
+        bad = KEEP - 1
+        if isinstance(src_of, np.ndarray) and src_of.dtype.kind in "iu":   # (no per-entry loop)
+            if src_of.dtype.kind == "u":
+                wide = src_of.astype(np.uint64)
+                wide = np.where(wide > KEEP, np.uint64(bad), wide)
+            else:
+                wide = src_of.astype(np.int64)
+                wide = np.where(wide == -1, KEEP, np.where((wide < 0) | (wide > KEEP), bad, wide))
+            src = np.ascontiguousarray(wide.astype(np.uint32))
+        else:
+            ints = [-1 if s is None else int(s) for s in src_of]
+            src = np.array([KEEP if s == -1 else s if 0 <= s <= KEEP else bad for s in ints], np.uint32)
+        if src.shape != (self.n,):
+            raise ValueError("src_of must have %d entries" % self.n)
+        t, r = ctypes.c_double(0), ctypes.c_uint32(0)
+        self._check(lib().WasmEdge_BatchSnapshotRestoreSelected(self._h, snap._h, src.ctypes.data, ctypes.byref(r),
+                                                                ctypes.byref(t) if timed else None))
+        return t.value, int(r.value)
+
+    def restore_tensor(self, snap, src_of, timed=True):
+        """restore_selected() from a contiguous torch.int32 tensor [n] on the context's device
+        (WasmEdge_BatchSnapshotRestoreSelectedDevice): -1 keeps the instance, the convention of
+        func_of in set_calls_tensor; the map never crosses the host. Returns (kernel seconds,
+        instances restored). The same note on torch initialising the device before the first
+        BatchContext applies as for set_args_tensor."""
+        torch = self._slot_tensor(src_of, None, "int32", "restore_tensor: src_of")
+        if not isinstance(snap, Snapshot) or not snap._h:
+            raise ValueError("a Snapshot that is not closed is needed")
+        # the library does not know the stream that produced the tensor
+        with torch.cuda.device(src_of.device):
+            torch.cuda.current_stream().synchronize()
+        t, r = ctypes.c_double(0), ctypes.c_uint32(0)
+        self._check(lib().WasmEdge_BatchSnapshotRestoreSelectedDevice(self._h, snap._h, src_of.data_ptr(),
+                                                                      ctypes.byref(r),
+                                                                      ctypes.byref(t) if timed else None))
+        return t.value, int(r.value)
 
     def total_costs(self):
         """Each instance's gas total (WasmEdge_BatchGetTotalCosts)."""

@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <mutex>
+#include <string>
 #include <vector>
 
 #include "batch_ctx.h"
@@ -19,6 +20,7 @@
 
 extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s);
 extern "C" hipError_t wb_launch_snap_rows(const SnapRowsParams *p, hipStream_t s);
+extern "C" hipError_t wb_launch_snap_plan(const SnapPlanParams *p, hipStream_t s);
 extern "C" hipError_t wb_launch_snap_stack(const SnapStackParams *p, int kind, hipStream_t s);
 extern "C" hipError_t wb_launch_snap_inst(const SnapInstParams *p, hipStream_t s);
 
@@ -64,6 +66,7 @@ struct WasmEdge_BatchSnapshot {
   // nothing of its own to free while its kernels run)
   mutable wbs::RestorePlan plan;
   mutable DevBuf<uint32_t> plan_src, plan_wave;
+  mutable DevBuf<uint32_t> plan_sum;       // a device map's plan: the summary (SnapPlanParams)
   mutable std::vector<uint32_t> gs_plan;   // (snapshot_plan.h plan_stack)
   mutable DevBuf<uint32_t> gs_plan_d;
 };
@@ -174,6 +177,24 @@ bool capture_invocation(Ctx *C, Snap *S) {
   return true;
 }
 
+// Instances that hold pool rows (the caller settled and waited for the stream): the reserved
+// layout takes them (hostcall.cpp grow_layout). false, with the message, when it cannot or on
+// a device error; the context stays as it was.
+bool take_pool_rows(Ctx *C) {
+  if (!C->grow_host || !C->pool_used) return true;
+  std::vector<uint32_t> pages;
+  if (!fetch_slot(C, LS_PAGES, &pages)) return false;
+  uint32_t reached = 0;
+  for (uint32_t i = 0; i < C->n; i++) reached = std::max(reached, pages[i]);
+  if (reached > C->rpages && !grow_layout(C, reached, reached, true)) return false;
+  if (reached > C->rpages) {
+    C->last_error = "snapshot: instances hold pages past the reserved layout, which cannot grow to take "
+                    "them (device memory, MemoryPoolBytes or WB_RELAYOUT=0)";
+    return false;
+  }
+  return true;
+}
+
 Snap *create_one(Ctx *C, uint8_t *code, bool inv) {
   DevScope dev(C);
   const wb::Program &P = C->prog;
@@ -183,18 +204,7 @@ Snap *create_one(Ctx *C, uint8_t *code, bool inv) {
   if (!C->settle() || !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot")) return nullptr;
   // instances that hold pool rows: the reserved layout takes them (hostcall.cpp grow_layout),
   // so that a snapshot never holds a page at or above the rpages it records
-  if (C->grow_host && C->pool_used) {
-    std::vector<uint32_t> pages;
-    if (!fetch_slot(C, LS_PAGES, &pages)) return nullptr;
-    uint32_t reached = 0;
-    for (uint32_t i = 0; i < C->n; i++) reached = std::max(reached, pages[i]);
-    if (reached > C->rpages && !grow_layout(C, reached, reached, true)) return nullptr;
-    if (reached > C->rpages) {
-      C->last_error = "snapshot: instances hold pages past the reserved layout, which cannot grow to take "
-                      "them (device memory, MemoryPoolBytes or WB_RELAYOUT=0)";
-      return nullptr;
-    }
-  }
+  if (!take_pool_rows(C)) return nullptr;
   std::unique_ptr<Snap> S(new Snap());
   S->device = C->device;
   S->n = C->n;
@@ -267,9 +277,35 @@ void delete_one(Snap *S) {
   if (sw) (void)hipSetDevice(cur);
 }
 
+// NumInstances words from Buf on lie inside an allocation on the context's device, as far as
+// this HIP runtime knows the allocation (hostcall.cpp mem_io: one it does not know, a
+// framework's with a runtime of its own, is the caller's word)
+bool device_map_ok(Ctx *C, const uint32_t *Buf) {
+  DevScope dev(C);
+  hipPointerAttribute_t at{};
+  void *base = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttributes(&at, Buf) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
+    (void)hipGetLastError();
+    return true;
+  }
+  if (at.type != hipMemoryTypeDevice || at.device != C->device ||
+      hipMemGetAddressRange(&base, &size, const_cast<uint32_t *>(Buf)) != hipSuccess) {
+    (void)hipGetLastError();
+    C->fail(kRuntimeError, "restore: the map is not a buffer on the context's device");
+    return false;
+  }
+  const uint64_t room = uint64_t(size) - uint64_t(reinterpret_cast<const uint8_t *>(Buf) - static_cast<uint8_t *>(base));
+  if (room < uint64_t(C->n) * 4) {
+    C->fail(kRuntimeError, "restore: the device map is smaller than NumInstances words");
+    return false;
+  }
+  return true;
+}
+
 uint8_t rows_launch(Ctx *C, uint32_t *dst, const uint32_t *src, const uint32_t *src_of, uint32_t words_d,
                     uint32_t words_s, uint32_t base_d, uint32_t base_s, uint32_t count, uint32_t g,
-                    uint32_t fill, uint32_t ls_fix) {
+                    uint32_t fill, uint32_t ls_fix, bool keep) {
   SnapRowsParams r{};
   r.dst = dst;
   r.src = src;
@@ -283,25 +319,103 @@ uint8_t rows_launch(Ctx *C, uint32_t *dst, const uint32_t *src, const uint32_t *
   r.g = g;
   r.fill = fill;
   r.ls_fix = ls_fix;
+  r.keep = keep ? 1 : 0;
   return C->hip_ok(wb_launch_snap_rows(&r, C->stream), "restore") ? 0 : kRuntimeError;
 }
 
-uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *KernelSeconds) {
+// What kept lanes need before a restore changes anything (DESIGN.md "Selective restore"): a
+// deferred Reset carried out, the pool rows taken into the reserved layout. false, with the
+// message, when that cannot be done; the context stays as it was. Doing it again is harmless.
+bool prepare_keep(Ctx *C) {
+  DevScope dev(C);
+  return C->settle() && C->hip_ok(hipStreamSynchronize(C->stream), "restore") && take_pool_rows(C);
+}
+
+const char *const kKeepInvocation =
+    "restore: a map that keeps instances cannot go with a snapshot that holds an invocation "
+    "(SnapshotCreateSuspended)";
+
+// The plan of a restore through SrcDev, a map on the device (wb_snap_plan_kernel), into
+// S->plan_src / S->plan_wave; sum: its summary, read back with one synchronise.
+bool device_plan(Ctx *C, const Snap *S, const uint32_t *SrcDev, bool same, uint32_t sum[4]) {
+  if ((!S->plan_src.ptr && !S->plan_src.alloc(size_t(C->nwaves) * 64)) ||
+      (!S->plan_wave.ptr && !S->plan_wave.alloc(size_t(C->nwaves) * 2)) ||
+      (!S->plan_sum.ptr && !S->plan_sum.alloc(4))) {
+    (void)hipGetLastError();
+    C->last_error = "restore: no device memory";
+    return false;
+  }
+  SnapPlanParams q{};
+  q.map = SrcDev;
+  q.snap_rows = S->rows.ptr;
+  q.plan_src = S->plan_src.ptr;
+  q.wave_plan = S->plan_wave.ptr;
+  q.summary = S->plan_sum.ptr;
+  q.n = C->n;
+  q.nwaves = C->nwaves;
+  q.same_granule = same ? 1 : 0;
+  return C->hip_ok(hipMemsetAsync(S->plan_sum.ptr, 0, 16, C->stream), "restore") &&
+         C->hip_ok(wb_launch_snap_plan(&q, C->stream), "restore") &&
+         C->hip_ok(hipMemcpyAsync(sum, S->plan_sum.ptr, 16, hipMemcpyDeviceToHost, C->stream), "restore") &&
+         C->hip_ok(hipStreamSynchronize(C->stream), "restore");
+}
+
+// SrcOf: the map on the host, SrcDev: on the device (at most one; both NULL: every instance
+// from itself). selected: an entry may be wbs::kKeep (WasmEdge_BatchSnapshotRestoreSelected).
+uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, const uint32_t *SrcDev, bool selected,
+                    uint32_t *Restored, double *KernelSeconds) {
   const wb::Program &P = C->prog;
+  bool any_keep = false, gather = false;
+  uint32_t restored = C->n;
   if (SrcOf)
-    for (uint32_t i = 0; i < C->n; i++)
-      if (SrcOf[i] >= C->n) return C->fail(kWrongVMWorkflow, "restore: SrcOf names an instance past NumInstances");
+    for (uint32_t i = 0; i < C->n; i++) {
+      if (selected && SrcOf[i] == wbs::kKeep) any_keep = true;
+      else if (SrcOf[i] >= C->n)
+        return C->fail(kWrongVMWorkflow, selected ? "restore: SrcOf holds an entry that is neither KEEP nor below NumInstances"
+                                                  : "restore: SrcOf names an instance past NumInstances");
+    }
+  if (any_keep && S->has_inv) return C->fail(kWrongVMWorkflow, kKeepInvocation);
   // the layout now against the one recorded: the reserved layout and the tables only grow
-  const uint32_t mw = P.has_mem ? C->mem_words : 0;
   bool fits = S->n == C->n && S->ls_slots == C->ls_slots && S->xwords == C->xwords && S->xlog == C->xlog &&
               S->tabinfo.size() == P.tabinfo.size() && (!P.has_mem || S->mem_words <= C->mem_words) && !C->mem_fresh;
   for (size_t t = 0; fits && S->tab_words && 2 * t + 1 < S->tabinfo.size(); t++)
     fits = S->tabinfo[2 * t + 1] <= P.tabinfo[2 * t + 1];
   if (!fits) return C->fail(kRuntimeError, "restore: the context's layout cannot hold the snapshot");
   DevScope dev(C);
-  const bool same = S->mlog == C->mlog;
-  const bool planned = SrcOf || !same;
-  if (planned) wbs::plan_restore(SrcOf, C->n, C->nwaves, S->rows_h.data(), same, &S->plan);
+  // A map on the device. The host-side WASI lane state and the host mirrors of an invocation
+  // (call_func, call_status, susp_h) need the map on the host: it is read back once and takes
+  // the host path. Otherwise the device plans, and nothing that changes state is launched
+  // before its summary is here.
+  if (SrcDev && (S->has_inv || !S->wasi.empty())) {
+    std::vector<uint32_t> map(C->n);
+    if (!C->hip_ok(hipMemcpy(map.data(), SrcDev, size_t(C->n) * 4, hipMemcpyDeviceToHost), "restore"))
+      return kRuntimeError;
+    return restore_one(C, S, map.data(), nullptr, true, Restored, KernelSeconds);
+  }
+  bool same = S->mlog == C->mlog;
+  if (SrcDev) {
+    uint32_t sum[4] = {0, 0, 0, 0};
+    if (!device_plan(C, S, SrcDev, same, sum)) return kRuntimeError;
+    if (sum[0])
+      return C->fail(kWrongVMWorkflow, "restore: SrcOf holds an entry that is neither KEEP nor below NumInstances "
+                                       "(instance " + std::to_string(~sum[0]) + ")");
+    any_keep = sum[1] != 0;
+    gather = sum[2] != 0;
+    restored = sum[3];
+  }
+  // Kept lanes (DESIGN.md "Selective restore"). A Reset left to the next launch is carried
+  // out first, as a capture does: cancelled, the kept lanes would miss it. And a kept lane may
+  // hold pages past the reserved layout: the layout takes the pool rows as at a capture, so
+  // that pool_reset below has nothing of a kept lane to lose; when it cannot, nothing changed.
+  if (any_keep && !prepare_keep(C)) return kRuntimeError;   // (the granule is a Reset's to change: `same` holds)
+  const uint32_t mw = P.has_mem ? C->mem_words : 0;
+  const bool mapped = SrcOf || SrcDev;
+  const bool planned = mapped || !same;
+  if (planned && !SrcDev) {
+    wbs::plan_restore(SrcOf, C->n, C->nwaves, S->rows_h.data(), same, &S->plan);
+    gather = !S->plan.identity;
+    restored = S->plan.restored;
+  }
   // a suspended invocation: the call stack deep enough for the rows its sources hold (a Reset
   // since the capture returned it to its first depth) and the result rows at the captured
   // stride, before anything of the context's state changes
@@ -324,9 +438,9 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
   // every row below the waves' current bound itself and writes every state slot, and that
   // launch would otherwise wipe what it restored. A Reset that is queued orders before the
   // restore's kernels on the stream; nothing here reads instance state from the host, so an
-  // untimed restore does not wait for it.
+  // untimed restore does not wait for it. (With a kept lane it was carried out above.)
   C->reset_deferred = false;
-  if (planned) {
+  if (planned && !SrcDev) {
     if ((!S->plan_src.ptr && !S->plan_src.alloc(S->plan.src.size())) ||
         (!S->plan_wave.ptr && !S->plan_wave.alloc(S->plan.wave.size()))) {
       (void)hipGetLastError();
@@ -338,9 +452,10 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
                                   hipMemcpyHostToDevice, C->stream), "restore"))
       return kRuntimeError;
   }
-  const uint32_t *src_of = SrcOf ? S->plan_src.ptr : nullptr;
+  const uint32_t *src_of = mapped ? S->plan_src.ptr : nullptr;
   (void)hipEventRecord(C->ev0, C->stream);
-  // no restored lane needs a pool row (create_one): the context's go back
+  // no restored lane needs a pool row (create_one), and the layout took the kept lanes': the
+  // context's go back
   if (!pool_reset(C)) return kRuntimeError;
   SnapMemParams p{};
   p.mem = C->mem.ptr;
@@ -359,30 +474,32 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
   p.g_snap = S->mlog;
   // (the current bounds are the device's to read; the snapshot's rows size the grid)
   p.chunks = chunks_for(C->nwaves, S->max_tiles);
-  if (!C->hip_ok(wb_launch_snap_mem(&p, planned && !S->plan.identity ? 2 : 1, C->stream), "restore"))
+  if (!C->hip_ok(wb_launch_snap_mem(&p, (planned && gather ? 2 : 1) + (any_keep ? 2 : 0), C->stream), "restore"))
     return kRuntimeError;
   // the state slots after memory 0 (whose kernel read the current marks), "not parked"
   // (a suspended invocation keeps its resume points: LS_RPC / LS_GSP / LS_HBASE as captured)
   uint8_t e = rows_launch(C, C->lstate.ptr, S->lstate.ptr, src_of, C->ls_slots, S->ls_slots, 0, 0, C->ls_slots, 0, 0,
-                          S->has_inv ? 0 : 1);
+                          S->has_inv ? 0 : 1, any_keep);
   // per-lane tables, table by table: the capacities may have widened since (widen_tables);
   // the slots past the captured capacity are null
   for (uint32_t t = 0; !e && S->tab_words && t < P.ntables; t++) {
     const uint32_t fs = S->tabinfo[2 * t], cs = S->tabinfo[2 * t + 1], fc = P.tabinfo[2 * t], cc = P.tabinfo[2 * t + 1];
-    e = rows_launch(C, C->ltab.ptr, S->ltab.ptr, src_of, P.tab_words, S->tab_words, fc, fs, cs, 0, 0, 0);
-    if (!e && cc > cs)
-      e = rows_launch(C, C->ltab.ptr, nullptr, nullptr, P.tab_words, 0, fc + cs, 0, cc - cs, 0, 0xFFFFFFFFu, 0);
+    e = rows_launch(C, C->ltab.ptr, S->ltab.ptr, src_of, P.tab_words, S->tab_words, fc, fs, cs, 0, 0, 0, any_keep);
+    if (!e && cc > cs)   // (a kept lane's widened table keeps its slots: the map goes along)
+      e = rows_launch(C, C->ltab.ptr, nullptr, any_keep ? src_of : nullptr, P.tab_words, 0, fc + cs, 0, cc - cs, 0,
+                      0xFFFFFFFFu, 0, any_keep);
   }
   if (!e && !P.xmems.empty() && C->xwords)
-    e = rows_launch(C, C->xmem.ptr, S->xmem.ptr, src_of, C->xwords, S->xwords, 0, 0, C->xwords, C->xlog, 0, 0);
+    e = rows_launch(C, C->xmem.ptr, S->xmem.ptr, src_of, C->xwords, S->xwords, 0, 0, C->xwords, C->xlog, 0, 0,
+                    any_keep);
   const size_t xs = size_t(C->nwaves) * 64;
   for (size_t k = 0; !e && k < P.xmems.size(); k++)
-    e = rows_launch(C, C->xpages.ptr + k * xs, S->xpages.ptr + k * xs, src_of, 1, 1, 0, 0, 1, 0, 0, 0);
+    e = rows_launch(C, C->xpages.ptr + k * xs, S->xpages.ptr + k * xs, src_of, 1, 1, 0, 0, 1, 0, 0, 0, any_keep);
   // the suspended invocation: frame-save rows, the call-stack rows of the sources, and status,
   // count, hcall and result row of every instance
   if (!e && S->has_inv) {
     const uint32_t fw = uint32_t(P.total_cells() ? P.total_cells() : 1) + C->gs_lds;
-    e = rows_launch(C, C->fsave.ptr, S->fsave.ptr, src_of, fw, fw, 0, 0, fw, 0, 0, 0);
+    e = rows_launch(C, C->fsave.ptr, S->fsave.ptr, src_of, fw, fw, 0, 0, fw, 0, 0, 0, false);
     SnapStackParams k{};
     k.gstack = C->gstack.ptr;
     k.snap = S->gs.ptr;
@@ -411,11 +528,12 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
   }
   if (e) return e;
   (void)hipEventRecord(C->ev1, C->stream);
-  // the host-side WASI lane state through SrcOf; `index` and an instance's own args stay
+  // the host-side WASI lane state through SrcOf; `index` and an instance's own args stay, and
+  // a kept instance keeps its lane
   if (!S->wasi.empty() && S->wasi.size() == C->wasi_lanes.size()) {
     std::vector<wbw::Lane> lanes(C->n);
     for (uint32_t i = 0; i < C->n; i++) {
-      lanes[i] = S->wasi[SrcOf ? SrcOf[i] : i];
+      lanes[i] = SrcOf && SrcOf[i] == wbs::kKeep ? C->wasi_lanes[i] : S->wasi[SrcOf ? SrcOf[i] : i];
       lanes[i].index = C->wasi_lanes[i].index;
       lanes[i].own_args = C->wasi_lanes[i].own_args;
       lanes[i].args = C->wasi_lanes[i].args;
@@ -467,6 +585,7 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, double *Kernel
     (void)hipEventElapsedTime(&ms, C->ev0, C->ev1);
     *KernelSeconds = ms * 1e-3;
   }
+  if (Restored) *Restored = restored;
   return 0;
 }
 
@@ -534,7 +653,7 @@ WasmEdge_Result WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *C, const Wa
                                               const uint32_t *SrcOf, double *KernelSeconds) {
   if (!C || !S) return R(kWrongVMWorkflow);
   if (S->ctx != C) return R(C->fail(kWrongVMWorkflow, "restore: the snapshot was taken from another context"));
-  if (C->shards.empty()) return R(restore_one(C, S, SrcOf, KernelSeconds));
+  if (C->shards.empty()) return R(restore_one(C, S, SrcOf, nullptr, false, nullptr, KernelSeconds));
   if (SrcOf) {
     for (uint32_t i = 0; i < C->n; i++)
       if (SrcOf[i] >= C->n) return R(C->fail(kWrongVMWorkflow, "restore: SrcOf names an instance past NumInstances"));
@@ -545,7 +664,7 @@ WasmEdge_Result WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *C, const Wa
   for (size_t g = 0; g < C->shards.size(); g++) {
     if (!C->shards[g]) continue;
     double t = 0;
-    const uint8_t e = restore_one(C->shards[g], S->subs[g], nullptr, KernelSeconds ? &t : nullptr);
+    const uint8_t e = restore_one(C->shards[g], S->subs[g], nullptr, nullptr, false, nullptr, KernelSeconds ? &t : nullptr);
     if (e) {
       C->last_error = C->shards[g]->last_error;
       return R(e);
@@ -554,6 +673,72 @@ WasmEdge_Result WasmEdge_BatchSnapshotRestore(WasmEdge_BatchContext *C, const Wa
   }
   if (KernelSeconds) *KernelSeconds = secs;
   return R(0);
+}
+
+WasmEdge_Result WasmEdge_BatchSnapshotRestoreSelected(WasmEdge_BatchContext *C, const WasmEdge_BatchSnapshot *S,
+                                                      const uint32_t *SrcOf, uint32_t *NumRestored,
+                                                      double *KernelSeconds) {
+  if (!C || !S || !SrcOf) return R(kWrongVMWorkflow);
+  if (S->ctx != C) return R(C->fail(kWrongVMWorkflow, "restore: the snapshot was taken from another context"));
+  if (C->shards.empty()) return R(restore_one(C, S, SrcOf, nullptr, true, NumRestored, KernelSeconds));
+  // shards: legal when nothing crosses a device -- every entry KEEP or the instance itself;
+  // the map is sliced by the placement
+  bool keep = false, local = true;
+  for (uint32_t i = 0; i < C->n; i++) {
+    if (SrcOf[i] == wbs::kKeep) keep = true;
+    else if (SrcOf[i] >= C->n)
+      return R(C->fail(kWrongVMWorkflow, "restore: SrcOf holds an entry that is neither KEEP nor below NumInstances"));
+    else local = local && SrcOf[i] == i;
+  }
+  if (keep && S->has_inv) return R(C->fail(kWrongVMWorkflow, kKeepInvocation));
+  if (!local)
+    return R(C->fail(kRuntimeError, "restore: SrcOf on a multi-device context (rows cannot cross devices); "
+                                    "every entry must be KEEP or the instance itself"));
+  std::vector<std::vector<uint32_t>> maps(C->shards.size());
+  for (size_t g = 0; g < C->shards.size(); g++)
+    if (C->shards[g]) maps[g].resize(C->shards[g]->n);
+  for (uint32_t i = 0; i < C->n; i++) {
+    Ctx *sh = nullptr;
+    uint32_t at = 0;
+    if (!wbm::route(C, i, &sh, &at)) return R(C->fail(kRuntimeError, "restore: an instance without a shard"));
+    for (size_t g = 0; g < C->shards.size(); g++)
+      if (C->shards[g] == sh) maps[g][at] = SrcOf[i] == wbs::kKeep ? wbs::kKeep : at;
+  }
+  // what can fail for want of room (a kept lane's pool rows) on every shard before the first
+  // restore, so that such a failure leaves all shards as they were
+  for (size_t g = 0; keep && g < C->shards.size(); g++)
+    if (C->shards[g] && !prepare_keep(C->shards[g])) {
+      C->last_error = C->shards[g]->last_error;
+      return R(kRuntimeError);
+    }
+  double secs = 0;
+  uint32_t total = 0;
+  for (size_t g = 0; g < C->shards.size(); g++) {
+    if (!C->shards[g]) continue;
+    double t = 0;
+    uint32_t r = 0;
+    const uint8_t e = restore_one(C->shards[g], S->subs[g], maps[g].data(), nullptr, true, &r, KernelSeconds ? &t : nullptr);
+    if (e) {
+      C->last_error = C->shards[g]->last_error;
+      return R(e);
+    }
+    secs = std::max(secs, t);
+    total += r;
+  }
+  if (KernelSeconds) *KernelSeconds = secs;
+  if (NumRestored) *NumRestored = total;
+  return R(0);
+}
+
+WasmEdge_Result WasmEdge_BatchSnapshotRestoreSelectedDevice(WasmEdge_BatchContext *C, const WasmEdge_BatchSnapshot *S,
+                                                            const uint32_t *SrcOfDevice, uint32_t *NumRestored,
+                                                            double *KernelSeconds) {
+  if (!C || !S || !SrcOfDevice) return R(kWrongVMWorkflow);
+  if (S->ctx != C) return R(C->fail(kWrongVMWorkflow, "restore: the snapshot was taken from another context"));
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "restore: a device map on a multi-device context (use the host entry)"));
+  if (!device_map_ok(C, SrcOfDevice)) return R(kRuntimeError);
+  return R(restore_one(C, S, nullptr, SrcOfDevice, true, NumRestored, KernelSeconds));
 }
 
 uint64_t WasmEdge_BatchSnapshotGetBytes(const WasmEdge_BatchSnapshot *S) { return S ? S->bytes : 0; }

@@ -35,8 +35,10 @@ struct SnapMemParams {
   const uint32_t *snap_rows;   // [nwaves] multiples of 64, <= mem_words
   const uint32_t *lstate;      // KParams::lstate: the waves' current marks (restore)
   const uint32_t *image;       // the module image (image_words words)
-  const uint32_t *src;         // [nwaves * 64] source instance of every lane (gather)
-  const uint32_t *wave_plan;   // [nwaves][2]: wbs::WaveClass, tiles its sources hold (gather)
+  const uint32_t *src;         // [nwaves * 64] source instance of every lane, or wbs::kKeep (gather)
+  const uint32_t *wave_plan;   // [nwaves][2]: wbs::WaveClass (| wbs::kHasKeep), tiles the sources
+                               // of its restored lanes hold (gather; a copy that keeps lanes
+                               // reads it for wbs::kKeepAll alone)
   uint32_t nwaves, mem_words, ls_slots, image_words;
   uint32_t g_mem, g_snap;      // log2 words per granule: the layout's now, the snapshot's
   uint32_t chunks;             // blocks per wave; block (w, c) takes tiles c, c + chunks, ...
@@ -76,12 +78,27 @@ struct SnapInstParams {
 // Whole-buffer state (instance-state slots, per-lane tables, memories 1..7, their sizes):
 // word base_d + k (k < count) of lane l of wave w, in a [wave][words][64] buffer interleaved
 // in granules of 2^g words, from the same word (at base_s) of its source lane -- or `fill`
-// when src is NULL. g > 0 needs base_d, base_s and count multiples of 2^g.
+// when src is NULL. g > 0 needs base_d, base_s and count multiples of 2^g. A lane whose src_of
+// entry is wbs::kKeep (keep != 0: a selective restore) is left as it is, fill included.
 struct SnapRowsParams {
   uint32_t *dst;
   const uint32_t *src;         // or NULL: fill
   const uint32_t *src_of;      // [nwaves * 64] or NULL: every lane from itself
   uint32_t nwaves, words_d, words_s, base_d, base_s, count, g, fill;
-  uint32_t ls_fix;             // 1: instance state -- LS_RPC / LS_GSP / LS_HBASE "not parked"
-                               // (0 for a snapshot that holds the invocation: kept as captured)
+  uint32_t ls_fix;             // 1: instance state -- LS_RPC / LS_GSP / LS_HBASE "not parked", kept
+                               // lanes included (0 for a snapshot that holds the invocation:
+                               // kept as captured)
+  uint32_t keep;               // 1: src_of may hold wbs::kKeep (wb_snap_select_rows_kernel)
+};
+
+// The plan of a selective restore from a source map on the device (wb_snap_plan_kernel): what
+// wbs::plan_restore makes on the host, written where the host's plan is uploaded.
+struct SnapPlanParams {
+  const uint32_t *map;         // [n] the caller's: a source instance or wbs::kKeep
+  const uint32_t *snap_rows;   // [nwaves] (SnapMemParams)
+  uint32_t *plan_src;          // [nwaves * 64] out: RestorePlan::src
+  uint32_t *wave_plan;         // [nwaves][2] out: RestorePlan::wave
+  uint32_t *summary;           // [4], zeroed by the caller: ~(the lowest invalid i) or 0, any lane
+                               // kept, any wave for the gather kernel, instances restored
+  uint32_t n, nwaves, same_granule;
 };

@@ -13,6 +13,11 @@
 //     a tile at a time through LDS;
 //   * wb_snap_rows_kernel: the small whole buffers (instance state, per-lane tables, memories
 //     1..7 and their sizes) through the same source map.
+// A selective restore (DESIGN.md "Selective restore") leaves the lanes its map keeps as they
+// are. It launches kernels of its own -- wb_snap_select_copy / _gather / _rows_kernel, the same
+// bodies instantiated with the kept-lane paths --, so that a restore without kept lanes runs
+// the kernels it always ran, and adds
+//   * wb_snap_plan_kernel: the plan of a restore from a source map that lives on the device.
 // A snapshot that holds a suspended invocation (DESIGN.md "Snapshots of suspended runs") adds
 //   * wb_snap_stack_capture_kernel / wb_snap_stack_copy_kernel: the HBM rows of the call stack
 //     that a wave's parked lanes own, packed the same way, out and back as they lie;
@@ -30,6 +35,9 @@
 
 #define WB_SNAP_FN __device__ inline
 #define WB_SNAP_SYNC() __syncthreads()
+#define WB_SNAP_ATOMIC_MAX(p, v) atomicMax((p), (v))
+#define WB_SNAP_ATOMIC_OR(p, v) atomicOr((p), (v))
+#define WB_SNAP_ATOMIC_ADD(p, v) atomicAdd((p), (v))
 
 namespace {
 
@@ -41,7 +49,12 @@ __global__ void __launch_bounds__(256) wb_snap_capture_kernel(const SnapMemParam
 
 __global__ void __launch_bounds__(256) wb_snap_restore_copy_kernel(const SnapMemParams p) {
   __shared__ uint32_t s_m[64];
-  snap_restore_copy_body(p, blockIdx.x, threadIdx.x, s_m);
+  snap_restore_copy_body<false>(p, blockIdx.x, threadIdx.x, s_m);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_select_copy_kernel(const SnapMemParams p) {
+  __shared__ uint32_t s_m[64];
+  snap_restore_copy_body<true>(p, blockIdx.x, threadIdx.x, s_m);
 }
 
 __global__ void __launch_bounds__(256) wb_snap_restore_gather_kernel(const SnapMemParams p) {
@@ -50,8 +63,24 @@ __global__ void __launch_bounds__(256) wb_snap_restore_gather_kernel(const SnapM
   snap_restore_gather_body(p, blockIdx.x, threadIdx.x, tile, s_m, s_src);
 }
 
+__global__ void __launch_bounds__(256) wb_snap_select_gather_kernel(const SnapMemParams p) {
+  __shared__ uint32_t tile[64 * kSnapPitch];
+  __shared__ uint32_t s_m[64], s_src[64], s_keep[64];
+  snap_select_gather_body(p, blockIdx.x, threadIdx.x, tile, s_m, s_src, s_keep);
+}
+
 __global__ void __launch_bounds__(256) wb_snap_rows_kernel(const SnapRowsParams p) {
-  snap_rows_body(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
+  snap_rows_body<false>(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
+}
+
+__global__ void __launch_bounds__(256) wb_snap_select_rows_kernel(const SnapRowsParams p) {
+  snap_rows_body<true>(p, (size_t)blockIdx.x * 256u + threadIdx.x, (size_t)gridDim.x * 256u);
+}
+
+// the plan of a selective restore from a source map on the device: a block per wave
+__global__ void __launch_bounds__(64) wb_snap_plan_kernel(const SnapPlanParams p) {
+  __shared__ uint32_t s_src[64], s_tiles[64], s_bad[64];
+  snap_plan_body(p, blockIdx.x, threadIdx.x, s_src, s_tiles, s_bad);
 }
 
 // a suspended invocation (DESIGN.md "Snapshots of suspended runs"): the HBM rows of the call
@@ -90,13 +119,23 @@ extern "C" hipError_t wb_launch_snap_inst(const SnapInstParams *p, hipStream_t s
   return hipGetLastError();
 }
 
-// kind 0: capture, 1: restore (copy), 2: restore (gather); p->chunks blocks per wave
+// kind 0: capture, 1: restore (copy), 2: restore (gather), 3 / 4: the same for a restore that
+// keeps lanes (the wave plan is read by both); p->chunks blocks per wave
 extern "C" hipError_t wb_launch_snap_mem(const SnapMemParams *p, int kind, hipStream_t s) {
   if (p->nwaves == 0 || p->mem_words == 0 || p->chunks == 0) return hipSuccess;
   const dim3 grid(p->nwaves * p->chunks), block(256);
   if (kind == 0) hipLaunchKernelGGL(wb_snap_capture_kernel, grid, block, 0, s, *p);
   else if (kind == 1) hipLaunchKernelGGL(wb_snap_restore_copy_kernel, grid, block, 0, s, *p);
-  else hipLaunchKernelGGL(wb_snap_restore_gather_kernel, grid, block, 0, s, *p);
+  else if (kind == 2) hipLaunchKernelGGL(wb_snap_restore_gather_kernel, grid, block, 0, s, *p);
+  else if (kind == 3) hipLaunchKernelGGL(wb_snap_select_copy_kernel, grid, block, 0, s, *p);
+  else hipLaunchKernelGGL(wb_snap_select_gather_kernel, grid, block, 0, s, *p);
+  return hipGetLastError();
+}
+
+// the caller zeroed p->summary on the same stream
+extern "C" hipError_t wb_launch_snap_plan(const SnapPlanParams *p, hipStream_t s) {
+  if (p->nwaves == 0) return hipSuccess;
+  hipLaunchKernelGGL(wb_snap_plan_kernel, dim3(p->nwaves), dim3(64), 0, s, *p);
   return hipGetLastError();
 }
 
@@ -104,7 +143,8 @@ extern "C" hipError_t wb_launch_snap_rows(const SnapRowsParams *p, hipStream_t s
   const uint64_t total = (uint64_t)p->nwaves * p->count * 64u;
   if (total == 0) return hipSuccess;
   const uint64_t blocks = (total + 1023u) / 1024u;   // (4 words per thread where it is large)
-  hipLaunchKernelGGL(wb_snap_rows_kernel, dim3((uint32_t)(blocks < 65536u ? blocks : 65536u)), dim3(256), 0, s,
-                     *p);
+  const dim3 grid((uint32_t)(blocks < 65536u ? blocks : 65536u));
+  if (p->keep) hipLaunchKernelGGL(wb_snap_select_rows_kernel, grid, dim3(256), 0, s, *p);
+  else hipLaunchKernelGGL(wb_snap_rows_kernel, grid, dim3(256), 0, s, *p);
   return hipGetLastError();
 }

@@ -12,6 +12,10 @@
 
 namespace wbs {
 
+// a source-map entry of a selective restore (WASMEDGE_BATCH_SNAPSHOT_KEEP): the lane keeps
+// what it holds
+constexpr uint32_t kKeep = 0xFFFFFFFFu;
+
 // (rows_of_mark, the rows of a wave that can differ from zero given its highest write mark:
 // snapshot.h, shared with the kernels)
 
@@ -40,50 +44,69 @@ inline uint64_t pack_rows(const uint32_t *marks, uint32_t nwaves, uint32_t image
 // The captured instance that lane `inst` (of nwaves * 64, the last wave's lanes past n
 // included) restarts from. A lane past n never runs; it follows lane 0 of its wave into that
 // lane's source wave, keeping its own lane number, so that it does not turn a broadcast or a
-// permutation within a wave into a gather.
+// permutation within a wave into a gather. kKeep (a selective restore: the lane keeps what it
+// holds) is carried through, and a lane past n is kept when lane 0 of its wave is.
 inline uint32_t source_of(const uint32_t *src_of, uint32_t n, uint32_t inst) {
   if (!src_of) return inst;
   if (inst < n) return src_of[inst];
-  return (src_of[inst & ~63u] & ~63u) | (inst & 63u);
+  const uint32_t s0 = src_of[inst & ~63u];
+  return s0 == kKeep ? kKeep : (s0 & ~63u) | (inst & 63u);
 }
 
 enum WaveClass : uint32_t {
   kIdentity = 0,   // every lane from itself, same granule: tiles are copied as they lie
   kOneWave = 1,    // every lane from one source wave: its tile is read whole, permuted in LDS
   kGather = 2,     // lanes from several waves: every lane gathers its source lane's words
+  kKeepAll = 3,    // every lane kept (selective restore): the wave is not visited
 };
+// beside the class of a wave that restores some lanes and keeps others: its class is that of
+// its restored lanes alone, and the memory-0 restore writes it lane by lane (gather kernel)
+constexpr uint32_t kHasKeep = 0x100u, kClassMask = 0xFFu;
 
 struct RestorePlan {
-  std::vector<uint32_t> src;    // [nwaves * 64] source_of every lane
-  std::vector<uint32_t> wave;   // [nwaves][2]: WaveClass, tiles its sources hold (the largest)
+  std::vector<uint32_t> src;    // [nwaves * 64] source_of every lane (kKeep carried through)
+  std::vector<uint32_t> wave;   // [nwaves][2]: WaveClass (| kHasKeep), tiles the sources of its
+                                // restored lanes hold (the largest)
   uint32_t max_tiles = 0;       // the largest of those
-  bool identity = true;         // every wave kIdentity
+  bool identity = true;         // no wave needs the gather kernel: each is kIdentity without a
+                                // kept lane, or kKeepAll
+  bool any_keep = false;        // some lane (below n) is kept
+  uint32_t restored = 0;        // instances (below n) that are not kept
 };
 
 // snap_rows: [nwaves] rows each captured wave holds (multiples of kTile). Every src_of[i]
-// must be below n (the caller checked).
+// must be below n or kKeep (the caller checked).
 inline void plan_restore(const uint32_t *src_of, uint32_t n, uint32_t nwaves, const uint32_t *snap_rows,
                          bool same_granule, RestorePlan *P) {
   P->src.resize(size_t(nwaves) * 64);
   P->wave.assign(size_t(nwaves) * 2, 0);
   P->max_tiles = 0;
   P->identity = true;
+  P->any_keep = false;
+  P->restored = 0;
   for (uint32_t w = 0; w < nwaves; w++) {
     bool self = same_granule, one = true;
-    uint32_t tiles = 0;
+    uint32_t tiles = 0, kept = 0, first = kKeep;   // first: the source of the first restored lane
     for (uint32_t l = 0; l < 64; l++) {
       const uint32_t i = w * 64 + l, s = source_of(src_of, n, i);
       P->src[i] = s;
+      if (s == kKeep) {
+        kept++;
+        P->any_keep = P->any_keep || i < n;
+        continue;
+      }
+      if (i < n) P->restored++;
+      if (first == kKeep) first = s;
       self = self && s == i;
-      one = one && (s >> 6) == (P->src[size_t(w) * 64] >> 6);
+      one = one && (s >> 6) == (first >> 6);
       const uint32_t t = snap_rows[s >> 6] / kTile;
       tiles = t > tiles ? t : tiles;
     }
-    const uint32_t cls = self ? kIdentity : one ? kOneWave : kGather;
+    const uint32_t cls = kept == 64 ? kKeepAll : (self ? kIdentity : one ? kOneWave : kGather) | (kept ? kHasKeep : 0u);
     P->wave[2 * size_t(w)] = cls;
     P->wave[2 * size_t(w) + 1] = tiles;
     P->max_tiles = tiles > P->max_tiles ? tiles : P->max_tiles;
-    P->identity = P->identity && cls == kIdentity;
+    P->identity = P->identity && (cls == kIdentity || cls == kKeepAll);
   }
 }
 
