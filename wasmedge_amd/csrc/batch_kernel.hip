@@ -435,7 +435,7 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
       const uint32_t base = LS(LS_HBASE);
       for (uint32_t k = 0; k < nres; k++) F.set(base + k, p.hbuf[(size_t)inst * p.hb_cells + k]);
       // (BatchResume: a lane already at the new limit runs nothing and suspends again)
-      if (p.resume == 2u && count >= p.max_steps) status = WB_ERR_INTERRUPTED;
+      if (p.resume == 2u && (int64_t)count >= (int64_t)p.max_steps) status = WB_ERR_INTERRUPTED;
     } else {
       status = WB_STATUS_OK;
     }
@@ -521,7 +521,7 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
     // pass its budget by more than the run it is in
     uint32_t core_lim = 1u << 20;
     if (p.max_steps < (1ull << 62)) {
-      const uint64_t rem = count < p.max_steps ? p.max_steps - count : 1;
+      const uint64_t rem = (int64_t)count < (int64_t)p.max_steps ? p.max_steps - count : 1;
       const uint32_t r32 = (uint32_t)min(rem, (uint64_t)core_lim);
       core_lim = max(1u, wave_min_u32(status == WB_STATUS_RUNNING ? r32 : 0xFFFFFFFFu));
     }
@@ -849,7 +849,9 @@ __device__ __forceinline__ void interp(const KParams &p, Frame &F, const uint32_
       tpoll = now;
       stop = __hip_atomic_load(p.stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (status == WB_STATUS_RUNNING && (count >= p.max_steps || now - t0 > p.max_ticks || stop))
+    // (the count is compared signed: a taken branch's negative correction -- it skipped folded
+    // instructions that its target's count holds -- can carry it below zero for one round)
+    if (status == WB_STATUS_RUNNING && ((int64_t)count >= (int64_t)p.max_steps || now - t0 > p.max_ticks || stop))
       status = WB_ERR_INTERRUPTED;
   }
 #undef R32

@@ -303,7 +303,9 @@ static int emu_core(wb::Program &P, uint32_t entry, const uint32_t *calls, uint3
       GS(0) = DBC_EXIT_PC;
       gsp = 1;
       while (status == WB_STATUS_RUNNING) {
-        if (max_steps && count >= max_steps) { status = 0x07; break; }
+        // (signed: a taken branch's negative correction can carry the count below zero until
+        // the instruction at its target adds the folded instructions back)
+        if (max_steps && (int64_t)count >= (int64_t)max_steps) { status = 0x07; break; }
         const uint32_t pcs = pc;
         const DInstr I = P.code[pcs];
         const uint32_t w0 = I.w0, w1 = I.w1, w2 = I.w2, w3 = I.w3;
