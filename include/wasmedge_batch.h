@@ -712,6 +712,48 @@ WASMEDGE_BATCH_API WasmEdge_Result
 WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *Cxt, const uint32_t *Offsets,
                                  uint32_t Offset, const uint32_t *Lens, uint32_t Len, uint8_t *Dst,
                                  uint64_t Stride, uint8_t *PerInstance);
+/* Device-resident spans: the Device variants above with every instance's own offset and length
+ * read on the device, so that the pointer an instance's own run returned never crosses the
+ * host. Spans use the slot form of WasmEdge_BatchResultsDevice: instance i's own offset is the
+ * low 32 bits of OffsetSlots[i * OffsetStride], its length len_i the low 32 bits of
+ * LenSlots[i * LenStride]; the upper 32 bits are ignored, as BatchSetArgsDevice ignores them
+ * for an i32. A column of a results buffer is passed as it lies: a pointer to the column's
+ * first slot plus the row stride, in slots. NULL OffsetSlots: offset 0; NULL LenSlots: Len.
+ *
+ * Per instance exactly as the Device variants: the start is Offset + its own offset, computed
+ * in 64 bits; a range that ends past the instance's current size gives MemoryOutOfBounds
+ * (0x88) and moves nothing of that instance, neither its memory nor its row; status 0
+ * otherwise, also for len_i = 0 with the start within the size; a read leaves the bytes of a
+ * row past len_i untouched; writes persist until BatchReset. PerInstance is a DEVICE array
+ * [NumInstances] (NULL: no status bytes exist anywhere); *NumOutOfBounds (host, may be NULL)
+ * receives the number of instances given 0x88, so that a caller notices trouble without
+ * copying NumInstances bytes. Per call the host reads back a few words and no per-instance
+ * array; the library allocates nothing on the device after the context's first such call.
+ *
+ * Call-level failures, nothing moved -- the caller's rows, status bytes and memory stay as they
+ * were -- and a WasmEdge_BatchGetLastError message: WrongVMWorkflow (0x04) for a NULL context,
+ * NULL Src / Dst with Len != 0, Stride < Len, a slot pointer that is not 8-byte aligned, a
+ * non-NULL slot pointer with stride 0, or some len_i > Len (found on the device; the message
+ * names the lowest such i); 0x88 for a module without a memory; RuntimeError (0x02) for a
+ * multi-device context, or a rows / slots / status buffer that this HIP runtime knows not to be
+ * on the context's device or to be too short for NumInstances entries.
+ *
+ * Ordering as for the Device variants: the call orders after a BatchReset that did not wait,
+ * the CALLER synchronises whatever produced the buffers, the library synchronises its own
+ * stream before it returns. Not to be called from inside a host function. */
+WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchWriteMemoriesSpansDevice(
+    WasmEdge_BatchContext *Cxt, const uint64_t *OffsetSlots, uint64_t OffsetStride, uint32_t Offset,
+    const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len, const uint8_t *Src, uint64_t Stride,
+    uint8_t *PerInstance, uint32_t *NumOutOfBounds);
+WASMEDGE_BATCH_API WasmEdge_Result WasmEdge_BatchReadMemoriesSpansDevice(
+    WasmEdge_BatchContext *Cxt, const uint64_t *OffsetSlots, uint64_t OffsetStride, uint32_t Offset,
+    const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len, uint8_t *Dst, uint64_t Stride,
+    uint8_t *PerInstance, uint32_t *NumOutOfBounds);
+/* Waves (of 64 instances) of the last spans transfer that moved their bytes through the tiled
+ * path: every instance of the wave that moved bytes started at one 4-byte aligned address, with
+ * the rows' buffer and Stride 4-byte aligned too (DESIGN.md "Device-resident spans"). 0 for
+ * NULL and before any such call. A report: results never depend on it. */
+WASMEDGE_BATCH_API uint32_t WasmEdge_BatchGetLastSpansTiledWaves(const WasmEdge_BatchContext *Cxt);
 /* Instance snapshots: the state of EVERY instance as it stands between runs, held on the
  * device, and a restore that starts instance i from the captured state of instance SrcOf[i]
  * (SrcOf NULL: from its own) -- rewind after each try, fork, broadcast, survivor selection.

@@ -158,6 +158,8 @@ def lib():
             ("WasmEdge_BatchReadMemories", [vp, vp, u32, vp, u32, vp, u64, vp]),
             ("WasmEdge_BatchWriteMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
             ("WasmEdge_BatchReadMemoriesDevice", [vp, vp, u32, vp, u32, vp, u64, vp]),
+            ("WasmEdge_BatchWriteMemoriesSpansDevice", [vp, vp, u64, u32, vp, u64, u32, vp, u64, vp, vp]),
+            ("WasmEdge_BatchReadMemoriesSpansDevice", [vp, vp, u64, u32, vp, u64, u32, vp, u64, vp, vp]),
             ("WasmEdge_BatchSetArgsDevice", [vp, _String, vp, u32, vp, u64]),
             ("WasmEdge_BatchResultsDevice", [vp, vp, u32, u64, vp, vp]),
             ("WasmEdge_BatchSetCallsDevice", [vp, ctypes.POINTER(_String), u32, vp, vp, vp, vp, u64]),
@@ -223,6 +225,8 @@ def lib():
         L.WasmEdge_BatchGetCompiledRuns.argtypes = [vp]
         L.WasmEdge_BatchGetMemoryGranule.restype = u32
         L.WasmEdge_BatchGetMemoryGranule.argtypes = [vp]
+        L.WasmEdge_BatchGetLastSpansTiledWaves.restype = u32
+        L.WasmEdge_BatchGetLastSpansTiledWaves.argtypes = [vp]
         L.WasmEdge_BatchGetReservedPages.restype = u32
         L.WasmEdge_BatchGetReservedPages.argtypes = [vp]
         L.WasmEdge_BatchGetExtraMemoryPages.restype = u32
@@ -698,6 +702,65 @@ class BatchContext:
         """read_memories into such a tensor (bytes an instance does not fill stay as they
         are). Returns the status array."""
         return self._tensor_io(lib().WasmEdge_BatchReadMemoriesDevice, t, offset, offsets, lens)
+
+    # device-resident spans (WasmEdge_BatchWriteMemoriesSpansDevice / ReadMemoriesSpansDevice):
+    # the tensor variants above with every instance's own offset and length in int64 device
+    # tensors -- the slot form of results_tensor, so a column view res[:, k] is passed as it is
+    def _spans_tensor_io(self, fn, t, offsets, lens, offset, length, status):
+        import sys
+        torch = sys.modules.get("torch")
+        if torch is None or not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 \
+                or t.shape[0] != self.n or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError("a contiguous torch.uint8 tensor [%d, stride] on the device is needed" % self.n)
+        for what, x in (("offsets", offsets), ("lens", lens)):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor) or x.dtype != torch.int64 or x.dim() != 1 or x.shape[0] != self.n \
+                    or x.device != t.device or x.stride(0) <= 0:
+                raise ValueError("%s: a one-dimensional torch.int64 tensor [%d] with a positive stride, on the "
+                                 "device of the rows, is needed" % (what, self.n))
+        if status is not None and (not isinstance(status, torch.Tensor) or status.dtype != torch.uint8
+                                   or status.dim() != 1 or status.shape[0] != self.n
+                                   or not status.is_contiguous() or status.device != t.device):
+            raise ValueError("status: a contiguous torch.uint8 tensor [%d] on the device of the rows is needed" % self.n)
+        length = t.shape[1] if length is None else int(length)
+        if length < 0 or length > t.shape[1] or not 0 <= int(offset) < 1 << 32:
+            raise ValueError("length must lie within a row and offset within 32 bits")
+        # the library does not know the stream that produced (or will consume) the tensors
+        with torch.cuda.device(t.device):
+            torch.cuda.current_stream().synchronize()
+        oob = ctypes.c_uint32(0)
+        self._check(fn(self._h, offsets.data_ptr() if offsets is not None else None,
+                       offsets.stride(0) if offsets is not None else 0, int(offset),
+                       lens.data_ptr() if lens is not None else None, lens.stride(0) if lens is not None else 0,
+                       length, t.data_ptr() if t.numel() else None, t.shape[1],
+                       status.data_ptr() if status is not None else None, ctypes.addressof(oob)))
+        return int(oob.value)
+
+    def write_memories_spans_tensor(self, t, offsets=None, lens=None, offset=0, length=None, status=None):
+        """write_memories_tensor with the spans on the device: instance i writes the first
+        lens[i] (None: length; default: the row length) bytes of row i of t at offset +
+        offsets[i] (None: 0). offsets / lens: one-dimensional torch.int64 tensors of n elements
+        on t's device with any positive element stride -- a column view res[:, k] of a
+        results_tensor output is accepted as it is; the low 32 bits of an element count.
+        status: a contiguous torch.uint8 tensor [n] that receives 0 / 0x88 per instance, or
+        None (no status bytes exist). Returns the number of instances out of bounds. Nothing
+        per instance crosses the host. The same note on torch initialising the device before
+        the first BatchContext applies as for write_memories_tensor."""
+        return self._spans_tensor_io(lib().WasmEdge_BatchWriteMemoriesSpansDevice, t, offsets, lens, offset,
+                                     length, status)
+
+    def read_memories_spans_tensor(self, t, offsets=None, lens=None, offset=0, length=None, status=None):
+        """read_memories_tensor with the spans on the device (write_memories_spans_tensor):
+        bytes an instance does not fill stay as they are. Returns the number of instances out
+        of bounds."""
+        return self._spans_tensor_io(lib().WasmEdge_BatchReadMemoriesSpansDevice, t, offsets, lens, offset,
+                                     length, status)
+
+    def last_spans_tiled_waves(self):
+        """Waves of the last spans transfer that took the tiled path
+        (WasmEdge_BatchGetLastSpansTiledWaves). A report: results never depend on it."""
+        return lib().WasmEdge_BatchGetLastSpansTiledWaves(self._h)
 
     # device-resident arguments and results (WasmEdge_BatchSetArgsDevice / ResultsDevice): rows
     # of 64-bit slots, one per value and two per v128 (low half first), as int64 tensors

@@ -1696,6 +1696,54 @@ WasmEdge_Result WasmEdge_BatchReadMemoriesDevice(WasmEdge_BatchContext *C, const
   return bulk_memories(C, Offsets, Offset, Lens, Len, Dst, Stride, PerInstance, false, true);
 }
 
+// Device-resident spans (DESIGN.md "Device-resident spans"): the call-level checks the host
+// can make, then hostcall.cpp mem_spans (the lengths are checked on the device).
+static WasmEdge_Result spans_memories(WasmEdge_BatchContext *C, const uint64_t *OffsetSlots, uint64_t OffsetStride,
+                                      uint32_t Offset, const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len,
+                                      uint8_t *Buf, uint64_t Stride, uint8_t *PerInstance, uint32_t *NumOutOfBounds,
+                                      bool write) {
+  if (!C) return R(kWrongVMWorkflow);
+  const std::string what = write ? "BatchWriteMemoriesSpansDevice" : "BatchReadMemoriesSpansDevice";
+  if (!Buf && Len) return R(C->fail(kWrongVMWorkflow, what + (write ? ": null Src" : ": null Dst")));
+  if (Stride < Len) return R(C->fail(kWrongVMWorkflow, what + ": Stride is smaller than Len"));
+  if ((uintptr_t(OffsetSlots) | uintptr_t(LenSlots)) & 7u)
+    return R(C->fail(kWrongVMWorkflow, what + ": a slot pointer is not 8-byte aligned"));
+  if ((OffsetSlots && !OffsetStride) || (LenSlots && !LenStride))
+    return R(C->fail(kWrongVMWorkflow, what + ": a slot stride of 0"));
+  if ((OffsetSlots && OffsetStride > (~0ull >> 4)) || (LenSlots && LenStride > (~0ull >> 4)))
+    return R(C->fail(kWrongVMWorkflow, what + ": a slot stride out of range"));
+  if (!C->shards.empty())
+    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use the host variant"));
+  if (!C->prog.has_mem) return R(kMemoryOutOfBounds);
+  DevScope dev(C);
+  if (!device_rows_ok(C, OffsetSlots, 8, OffsetStride * 8, what.c_str()) ||
+      !device_rows_ok(C, LenSlots, 8, LenStride * 8, what.c_str()) ||
+      !device_rows_ok(C, Buf, Len, Stride, what.c_str()) || !device_rows_ok(C, PerInstance, 1, 1, what.c_str()))
+    return R(kRuntimeError);
+  return R(mem_spans(C, OffsetSlots, OffsetStride, Offset, LenSlots, LenStride, Len, Buf, Stride, PerInstance,
+                     NumOutOfBounds, write));
+}
+
+WasmEdge_Result WasmEdge_BatchWriteMemoriesSpansDevice(WasmEdge_BatchContext *C, const uint64_t *OffsetSlots,
+                                                       uint64_t OffsetStride, uint32_t Offset,
+                                                       const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len,
+                                                       const uint8_t *Src, uint64_t Stride, uint8_t *PerInstance,
+                                                       uint32_t *NumOutOfBounds) {
+  return spans_memories(C, OffsetSlots, OffsetStride, Offset, LenSlots, LenStride, Len, const_cast<uint8_t *>(Src),
+                        Stride, PerInstance, NumOutOfBounds, true);
+}
+
+WasmEdge_Result WasmEdge_BatchReadMemoriesSpansDevice(WasmEdge_BatchContext *C, const uint64_t *OffsetSlots,
+                                                      uint64_t OffsetStride, uint32_t Offset,
+                                                      const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len,
+                                                      uint8_t *Dst, uint64_t Stride, uint8_t *PerInstance,
+                                                      uint32_t *NumOutOfBounds) {
+  return spans_memories(C, OffsetSlots, OffsetStride, Offset, LenSlots, LenStride, Len, Dst, Stride, PerInstance,
+                        NumOutOfBounds, false);
+}
+
+uint32_t WasmEdge_BatchGetLastSpansTiledWaves(const WasmEdge_BatchContext *C) { return C ? C->spans_tiled : 0; }
+
 // ---- exported tables and globals (WasmEdge_TableInstance{Get,Set}Data / GetSize,
 // WasmEdge_GlobalInstance{Get,Set}Value, lib/api/wasmedge.cpp:2099-2139, 2273-2295),
 // per instance; Inst = WASMEDGE_BATCH_ALL_INSTANCES writes every instance

@@ -278,6 +278,14 @@ struct WasmEdge_BatchContext {
       if (slots > calls_res_slots) calls_res_slots = slots;
     }
   }
+  // device-resident spans (WasmEdge_BatchWriteMemoriesSpansDevice / ReadMemoriesSpansDevice,
+  // mem_spans.h): the plan kernel's lane and wave records and its summary -- two halves of 4
+  // words, one the call's (span_flip: the upper one), the other set by the call's plan to the
+  // values the next call starts from --, allocated at the first such call, and the
+  // waves of the last transfer that took the tiled path (WasmEdge_BatchGetLastSpansTiledWaves)
+  DevBuf<uint32_t> span_lane, span_wave, span_sum;
+  bool span_flip = false;
+  uint32_t spans_tiled = 0;
   // resumable runs (conf.Resumable; DESIGN.md "Resumable runs"): the invocation BatchResume
   // continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
   // Run / SnapshotRestore --, its entry pc, the cumulative step limit of the call in
@@ -444,6 +452,13 @@ uint8_t mem_rw(WasmEdge_BatchContext *C, uint32_t Inst, uint32_t Off, uint32_t L
 // PerInstance (host, or NULL): 0 / MemoryOutOfBounds per instance. 0 or RuntimeError.
 uint8_t mem_io(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offset, const uint32_t *Lens,
                uint32_t Len, uint8_t *Buf, uint64_t Stride, uint8_t *PerInstance, bool write, bool device);
+// device-resident spans (hostcall.cpp, mem_spans.hip): the same transfer with instance i's own
+// offset / length in the low halves of OffsetSlots[i * OffsetStride] / LenSlots[i * LenStride]
+// (device; NULL: 0 / Len) and PerInstance on the device (or NULL); *OutOfBounds: the instances
+// given 0x88. 0, WrongVMWorkflow (a length past Len: nothing moved) or RuntimeError.
+uint8_t mem_spans(WasmEdge_BatchContext *C, const uint64_t *OffsetSlots, uint64_t OffsetStride, uint32_t Offset,
+                  const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len, uint8_t *Buf, uint64_t Stride,
+                  uint8_t *PerInstance, uint32_t *OutOfBounds, bool write);
 // pool rows (hostcall.cpp): give wave `wave` rows up to `rows` pool pages (false: no
 // device memory for all of them; it keeps what it got); return every row at Reset
 bool pool_reserve(WasmEdge_BatchContext *C, uint32_t wave, uint32_t rows);

@@ -22,6 +22,7 @@
 
 #include "batch_ctx.h"
 #include "mem_io.h"
+#include "mem_spans.h"
 
 namespace wbh {
 
@@ -291,6 +292,78 @@ uint8_t mem_io(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offse
     }
   }
   if (PerInstance) memcpy(PerInstance, st.data(), n);
+  return 0;
+}
+
+// ---- device-resident spans (WasmEdge_BatchWriteMemoriesSpansDevice / ReadMemoriesSpansDevice) --
+// The same transfer with offsets, lengths and status bytes on the device (mem_spans.hip;
+// DESIGN.md "Device-resident spans"): the plan kernel, one readback of its summary -- a length
+// past Len must leave everything untouched, so nothing that moves bytes is launched before it
+// is here --, the move kernel. The plan's buffers live on the context: no allocation after the
+// first call, and no per-instance array crosses the host.
+uint8_t mem_spans(WasmEdge_BatchContext *C, const uint64_t *OffsetSlots, uint64_t OffsetStride, uint32_t Offset,
+                  const uint64_t *LenSlots, uint64_t LenStride, uint32_t Len, uint8_t *Buf, uint64_t Stride,
+                  uint8_t *PerInstance, uint32_t *OutOfBounds, bool write) {
+  DevScope dev(C);
+  if (!C->settle() || !pool_upload(C)) return kRuntimeError;
+  if (C->n == 0) {
+    if (OutOfBounds) *OutOfBounds = 0;
+    C->spans_tiled = 0;
+    return 0;
+  }
+  if (!C->span_sum.ptr) {
+    const uint32_t init[8] = {wbp::kNoBad, 0, 0, 0, wbp::kNoBad, 0, 0, 0};
+    if (!C->span_lane.alloc(size_t(C->nwaves) * 128) || !C->span_wave.alloc(size_t(C->nwaves) * 2) ||
+        !C->span_sum.alloc(8)) {
+      (void)hipGetLastError();
+      C->span_sum.alloc(0);
+      return C->fail(kRuntimeError, "memories: no device memory");
+    }
+    if (!C->hip_ok(hipMemcpy(C->span_sum.ptr, init, sizeof init, hipMemcpyHostToDevice), "memories")) {
+      C->span_sum.alloc(0);
+      return kRuntimeError;
+    }
+  }
+  MemSpanParams p{};
+  p.mem = C->mem.ptr;
+  p.lstate = C->lstate.ptr;
+  p.ptab = C->pt_w ? C->ptab.ptr : nullptr;
+  p.off_slots = OffsetSlots;
+  p.len_slots = LenSlots;
+  p.buf = Len ? Buf : nullptr;
+  p.status = PerInstance;
+  p.lane_plan = C->span_lane.ptr;
+  p.wave_plan = C->span_wave.ptr;
+  p.summary = C->span_sum.ptr + (C->span_flip ? 4 : 0);
+  p.next_summary = C->span_sum.ptr + (C->span_flip ? 0 : 4);
+  p.off_stride = OffsetStride;
+  p.len_stride = LenStride;
+  p.stride = Len ? Stride : 0;
+  p.mem_words = C->mem_words;
+  p.mlog = C->mlog;
+  p.ptab_w = C->pt_w;
+  p.ls_slots = C->ls_slots;
+  p.n = C->n;
+  p.nwaves = C->nwaves;
+  p.offset = Offset;
+  p.len = Len;
+  const uintptr_t bits = uintptr_t(p.buf) | uintptr_t(p.stride);
+  p.align = bits % 16 == 0 ? 16 : bits % 4 == 0 ? 4 : 1;
+  p.pieces = wbp::pieces_of(Len);
+  p.write = write ? 1 : 0;
+  uint32_t sum[4] = {0, 0, 0, 0};
+  if (!C->hip_ok(wb_launch_span_plan(&p, C->stream), "memories") ||
+      !C->hip_ok(hipMemcpyAsync(sum, p.summary, 16, hipMemcpyDeviceToHost, C->stream), "memories") ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "memories"))
+    return kRuntimeError;
+  C->span_flip = !C->span_flip;   // (the plan ran: the other half is ready, whatever comes of the call)
+  if (sum[0] != wbp::kNoBad)
+    return C->fail(kWrongVMWorkflow, "memories: the length of an instance exceeds Len (instance " + std::to_string(sum[0]) + ")");
+  if (!C->hip_ok(wb_launch_span_move(&p, C->stream), "memories") ||
+      !C->hip_ok(hipStreamSynchronize(C->stream), "memories"))
+    return kRuntimeError;
+  if (OutOfBounds) *OutOfBounds = sum[1];
+  C->spans_tiled = sum[2];
   return 0;
 }
 
