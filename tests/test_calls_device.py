@@ -526,6 +526,45 @@ def test_gpu_fingerprint_through_the_restage_rule(built, monkeypatch, blocks):
         ctx.close()
 
 
+@pytest.mark.gpu
+def test_gpu_restage_compares_with_what_lies_staged(built):
+    """The restage rule compares a restored invocation with the arguments that lie staged on the
+    device, not with the invocation restored last: a second restore under another staging still
+    wants a new one (0x04), and of two snapshots taken under two stagings and restored in turn
+    a Run is possible after exactly the one whose arguments are staged. Host staging, so every
+    CallsResultsDevice after a restore uploads the call vector again; it equals results()."""
+    from wasmedge_amd import batch
+    ctx = batch.BatchContext(SPIN, N, device=0, resumable=True)
+    snaps = []
+    try:
+        vecs = spin_vec(), spin_vec(flip_func=N - 1, flip_arg=N - 3)
+        want = []
+        for k, vec in enumerate(vecs):
+            stage_host(ctx, vec)
+            ctx.run()
+            want.append(both_reads_agree(ctx, 1, "run %d" % k))
+            snaps.append(ctx.snapshot(invocation=True))
+        assert not np.array_equal(want[0][1], want[1][1])   # (the flipped lane makes no call)
+        for _ in range(2):   # the second vector is the staged one
+            ctx.restore(snaps[0])
+            same(want[0], both_reads_agree(ctx, 1, "first restored"))
+        with pytest.raises(batch.WasmEdgeError) as e:
+            ctx.run()
+        assert e.value.code == 0x04
+        ctx.restore(snaps[1])
+        same(want[1], both_reads_agree(ctx, 1, "second restored"))
+        ctx.run()
+        same(want[1], both_reads_agree(ctx, 1, "second run again"))
+        ctx.restore(snaps[0])
+        stage_host(ctx, vecs[0])
+        ctx.run()
+        same(want[0], both_reads_agree(ctx, 1, "first staged and run again"))
+    finally:
+        for s in snaps:
+            s.close()
+        ctx.close()
+
+
 @pytest.fixture(scope="module")
 def tensor_child(built):
     """tests/calls_tensor_child.py, once: the torch mirror in a process where torch initialises

@@ -4,12 +4,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sig_layout.h"
+
 // A slot row (include/wasmedge_batch.h "device-resident arguments and results") is a
 // function's values back to back, one 64-bit slot each, a v128 two (low half first). The
 // device keeps arguments and results as 32-bit cells, [n][cells] row-major (kparams.h). A
 // per-signature table in device memory names, for every cell, the 32-bit word of the slot
 // row it is: entry = slot * 2 + half. Its length is the signature's, not the kernarg's.
-constexpr uint32_t kArgsNoCell = 0xFFFFFFFFu;   // unpack: a slot's upper word that reads zero
+// (sig_layout.h: the maps and kArgsNoCell)
 
 // slots -> KParams::params, and the arguments' fingerprint (args_fp_mix summed over all cells)
 struct ArgsPackParams {

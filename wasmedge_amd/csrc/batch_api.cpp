@@ -10,7 +10,6 @@
 #include <string>
 #include <vector>
 
-#include "args_io.h"
 #include "batch_ctx.h"
 #include "build/srchash.h"
 #include "jit.h"
@@ -369,10 +368,8 @@ uint8_t setup(WasmEdge_BatchContext *C, const uint8_t *wasm, uint32_t len) {
   C->hosts.assign(P.funcs.size(), {});
   C->hb_cells = 1;
   for (uint32_t f = 0; f < P.n_imported; f++) {
-    uint32_t a = 0, r = 0;
-    for (uint8_t t : P.types[P.funcs[f].type].params) a += wb::cells_of(t);
-    for (uint8_t t : P.types[P.funcs[f].type].results) r += wb::cells_of(t);
-    C->hb_cells = std::max(C->hb_cells, std::max(a, r));
+    const wb::SigLayout L = wb::layout_of(P.types[P.funcs[f].type]);
+    C->hb_cells = std::max(C->hb_cells, std::max(L.param_cells, L.result_cells));
   }
   if (!C->mem.alloc(nw * size_t(C->mem_words) * 64 + 64) ||
       !C->gstack.alloc(nw * size_t(C->gs_depth) * 64) ||
@@ -432,7 +429,7 @@ uint8_t layout_trial(WasmEdge_BatchContext *C, double secs) {
   for (uint64_t c : cnt) sum += double(c);
   const double rate = sum / secs;
   // (per-instance calls: the same call vector on the same arguments, not one function)
-  const uint64_t key = C->calls_on ? C->args_fp | (1ull << 63) : uint64_t(uint32_t(C->func));
+  const uint64_t key = C->staged.calls_on ? C->staged.args_fp | (1ull << 63) : uint64_t(uint32_t(C->staged.func));
   if (C->trial == 1) {
     C->trial_rate = rate;
     C->trial_key = key;
@@ -445,8 +442,6 @@ uint8_t layout_trial(WasmEdge_BatchContext *C, double secs) {
   }
   return 0;
 }
-
-uint32_t cells_of_value(uint8_t t) { return wb::cells_of(t); }
 
 // launch_once's entry_pc for per-instance calls (KParams::calls names each lane's): no
 // function's pc, so a wave order learned from one function is never taken for a call vector
@@ -487,9 +482,9 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
   k.status = C->status.ptr; k.counts = C->counts.ptr;
   k.n = C->n;
   k.entry_pc = entry_pc;
-  k.param_cells = is_start ? 0 : C->param_cells;
-  k.result_cells = is_start ? 0 : C->result_cells;
-  k.calls = !is_start && C->calls_on ? C->calls.ptr : nullptr;
+  k.param_cells = is_start ? 0 : C->staged.param_cells;
+  k.result_cells = is_start ? 0 : C->staged.result_cells;
+  k.calls = !is_start && C->staged.calls_on ? C->calls.ptr : nullptr;
   k.global_cells = P.global_cells;
   k.total_cells = P.total_cells() ? P.total_cells() : 1;
   k.table_size = uint32_t(P.table0.size());
@@ -576,7 +571,7 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
       // (per-instance calls: entry_pc is kCallsPc and the fingerprint covers the call
       // vector, so an order is reused only for an equal vector on equal arguments)
       const bool any_args = oae && oae[0] == '1' && !k.calls;
-      k.wave_order = C->order_pc == entry_pc && (C->order_fp == C->args_fp || any_args) && C->trial != 1 &&
+      k.wave_order = C->order_pc == entry_pc && (C->order_fp == C->staged.args_fp || any_args) && C->trial != 1 &&
                              C->trial != 3
                          ? C->wave_order.ptr : nullptr;
     }
@@ -616,7 +611,7 @@ uint8_t launch_once(WasmEdge_BatchContext *C, uint32_t entry_pc, bool is_start, 
       return kRuntimeError;
     C->order_pending = true;
     C->order_pc = entry_pc;
-    C->order_fp = C->args_fp;
+    C->order_fp = C->staged.args_fp;
     C->ctr_zero = true;
   }
   // the interpreter kernel's end
@@ -744,168 +739,6 @@ WasmEdge_BatchContext *WasmEdge_BatchCreateWithImports(const WasmEdge_BatchConfi
   return C;
 }
 
-WasmEdge_Result WasmEdge_BatchSetArgs(WasmEdge_BatchContext *C, const WasmEdge_String FuncName,
-                                      const WasmEdge_Value *Params, const uint32_t ParamLen) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty()) return wbm::set_args(C, FuncName, Params, ParamLen);
-  DevScope dev(C);
-  std::string name(FuncName.Buf ? FuncName.Buf : "", FuncName.Length);
-  int f = wb::find_export(C->prog, name);
-  if (f < 0) return R(C->fail(kFuncNotFound, "function '" + name + "' not found"));
-  const wb::FuncType &t = C->prog.types[C->prog.funcs[f].type];
-  // executor.cpp:88-100: parameter count and types must match
-  if (ParamLen != t.params.size()) return R(C->fail(kFuncSigMismatch, "parameter count mismatch"));
-  uint32_t pc = 0;
-  for (uint8_t ty : t.params) pc += cells_of_value(ty);
-  std::vector<uint32_t> cells(size_t(C->n) * (pc ? pc : 1));
-  for (uint32_t i = 0; i < C->n; i++) {
-    uint32_t at = 0;
-    for (uint32_t k = 0; k < ParamLen; k++) {
-      const WasmEdge_Value &v = Params[size_t(i) * ParamLen + k];
-      if (uint8_t(v.Type) != t.params[k])
-        return R(C->fail(kFuncSigMismatch, "parameter type mismatch"));
-      bool full = false;
-      const uint128_t x = t.params[k] == wb::EXTERNREF ? uint128_t(C->xref_in(v.Value, &full)) : v.Value;
-      if (full) return R(C->fail(kRuntimeError, "externref intern table full (2^31 - 1 values)"));
-      for (uint32_t q = 0; q < cells_of_value(t.params[k]); q++)
-        cells[size_t(i) * pc + at++] = uint32_t(x >> (32 * q));
-    }
-  }
-  uint32_t rc = 0;
-  for (uint8_t ty : t.results) rc += cells_of_value(ty);
-  // (the buffers stay when their sizes do: a caller passing new arguments every run pays no
-  // device allocation, and the kernel reads the same pages)
-  const size_t rn = size_t(C->n) * (rc ? rc : 1);
-  if ((C->params.n != cells.size() || !C->params.ptr) && !C->params.alloc(cells.size()))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if (!C->hip_ok(hipMemcpyAsync(C->params.ptr, cells.data(), cells.size() * 4,
-                                hipMemcpyHostToDevice, C->stream), "params upload"))
-    return R(kRuntimeError);
-  if (!C->hip_ok(hipStreamSynchronize(C->stream), "params upload")) return R(kRuntimeError);
-  // fingerprint of the arguments (the longest-first wave order is reused only on equal ones)
-  uint64_t fp = 0x9E3779B97F4A7C15ull ^ uint64_t(f);
-  for (uint32_t c : cells) fp = (fp ^ c) * 0x100000001B3ull + (fp >> 29);
-  C->args_fp = fp;
-  C->func = f;
-  C->param_cells = pc;
-  C->result_cells = rc;
-  C->result_types = t.results;
-  C->calls_on = false;   // (back to one function for every instance)
-  C->restage = false;
-  C->end_invocation();   // (new staging: a suspended invocation cannot continue)
-  return R(0);
-}
-
-// Per-instance calls: N independent VMExecute calls (vm.cpp:287-308 resolves each name,
-// executor.cpp:88-100 checks each signature), so an unknown name or a mismatch is that
-// instance's outcome, not the call's. Everything is checked and packed before anything of
-// the context changes: a failed call leaves the previous staging as it was.
-WasmEdge_Result WasmEdge_BatchSetCalls(WasmEdge_BatchContext *C, const WasmEdge_String *FuncNames,
-                                       const uint32_t NumFuncs, const uint32_t *FuncOf,
-                                       const WasmEdge_Value *Params, const uint32_t ParamStride,
-                                       const uint32_t *ParamLens) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!FuncOf || (NumFuncs && !FuncNames)) return R(C->fail(kWrongVMWorkflow, "BatchSetCalls: null FuncOf / FuncNames"));
-  for (uint32_t i = 0; i < C->n; i++)
-    if (FuncOf[i] != WASMEDGE_BATCH_NO_CALL && FuncOf[i] >= NumFuncs)
-      return R(C->fail(kWrongVMWorkflow, "BatchSetCalls: FuncOf[" + std::to_string(i) + "] names no function"));
-  if (!C->shards.empty()) return wbm::set_calls(C, FuncNames, NumFuncs, FuncOf, Params, ParamStride, ParamLens);
-  DevScope dev(C);
-  const wb::Program &P = C->prog;
-  std::vector<int> fidx(NumFuncs, -1);
-  std::vector<uint32_t> fpc(NumFuncs, 0), frc(NumFuncs, 0);
-  for (uint32_t j = 0; j < NumFuncs; j++) {
-    fidx[j] = wb::find_export(P, std::string(FuncNames[j].Buf ? FuncNames[j].Buf : "", FuncNames[j].Length));
-    if (fidx[j] < 0) continue;
-    const wb::FuncType &t = P.types[P.funcs[fidx[j]].type];
-    for (uint8_t ty : t.params) fpc[j] += cells_of_value(ty);
-    for (uint8_t ty : t.results) frc[j] += cells_of_value(ty);
-  }
-  // each instance's function, or the status it sits the run out with
-  std::vector<int32_t> cfunc(C->n, -1);
-  std::vector<uint8_t> cstat(C->n, 0);
-  uint32_t pc = 0, rc = 0;
-  bool import = false;
-  for (uint32_t i = 0; i < C->n; i++) {
-    const uint32_t j = FuncOf[i];
-    if (j == WASMEDGE_BATCH_NO_CALL) continue;
-    if (fidx[j] < 0) { cstat[i] = kFuncNotFound; continue; }
-    const wb::FuncType &t = P.types[P.funcs[fidx[j]].type];
-    const uint32_t len = ParamLens ? ParamLens[i] : ParamStride;
-    bool ok = len == t.params.size() && len <= ParamStride && (len == 0 || Params);
-    for (uint32_t k = 0; ok && k < len; k++) ok = uint8_t(Params[size_t(i) * ParamStride + k].Type) == t.params[k];
-    if (!ok) { cstat[i] = kFuncSigMismatch; continue; }
-    cfunc[i] = fidx[j];
-    pc = std::max(pc, fpc[j]);
-    rc = std::max(rc, frc[j]);
-    import |= P.funcs[fidx[j]].imported;
-  }
-  std::vector<uint32_t> cells(size_t(C->n) * (pc ? pc : 1)), tab(size_t(C->n) * 2);
-  for (uint32_t i = 0; i < C->n; i++) {
-    tab[2 * i] = WB_CALL_SKIP | cstat[i];
-    tab[2 * i + 1] = 0;
-    if (cfunc[i] < 0) continue;
-    const wb::FuncInfo &F = P.funcs[cfunc[i]];
-    const wb::FuncType &t = P.types[F.type];
-    uint32_t at = 0;
-    for (uint32_t k = 0; k < t.params.size(); k++) {
-      const WasmEdge_Value &v = Params[size_t(i) * ParamStride + k];
-      bool full = false;
-      const uint128_t x = t.params[k] == wb::EXTERNREF ? uint128_t(C->xref_in(v.Value, &full)) : v.Value;
-      if (full) return R(C->fail(kRuntimeError, "externref intern table full (2^31 - 1 values)"));
-      for (uint32_t q = 0; q < cells_of_value(t.params[k]); q++)
-        cells[size_t(i) * pc + at++] = uint32_t(x >> (32 * q));
-    }
-    tab[2 * i] = F.imported ? WB_CALL_SKIP : F.entry_pc;   // (an import: BatchRun refuses)
-    tab[2 * i + 1] = at;
-  }
-  const size_t rn = size_t(C->n) * (rc ? rc : 1);
-  if ((C->params.n != cells.size() || !C->params.ptr) && !C->params.alloc(cells.size()))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if (!C->calls.ptr && !C->calls.alloc(tab.size())) return R(C->fail(kRuntimeError, "device allocation failed"));
-  if (!C->hip_ok(hipMemcpyAsync(C->params.ptr, cells.data(), cells.size() * 4, hipMemcpyHostToDevice,
-                                C->stream), "params upload") ||
-      !C->hip_ok(hipMemcpyAsync(C->calls.ptr, tab.data(), tab.size() * 4, hipMemcpyHostToDevice,
-                                C->stream), "calls upload") ||
-      !C->hip_ok(hipStreamSynchronize(C->stream), "params upload"))
-    return R(kRuntimeError);
-  // fingerprint of the call vector and the arguments (wave order, layout trial)
-  uint64_t fp = 0xC2B2AE3D27D4EB4Full;
-  for (uint32_t c : tab) fp = (fp ^ c) * 0x100000001B3ull + (fp >> 29);
-  for (uint32_t c : cells) fp = (fp ^ c) * 0x100000001B3ull + (fp >> 29);
-  C->args_fp = fp;
-  C->func = -1;
-  C->param_cells = pc;
-  C->result_cells = rc;
-  C->result_types.clear();
-  C->call_func.swap(cfunc);
-  C->call_status.swap(cstat);
-  C->call_host_ok = true;    // (calls_io: the device copy of call_func is stale)
-  C->call_dev_ok = false;
-  C->calls_shape();
-  C->calls_import = import;
-  C->calls_on = true;
-  C->restage = false;
-  C->end_invocation();
-  return R(0);
-}
-
-WasmEdge_Result WasmEdge_BatchGetReturnLens(WasmEdge_BatchContext *C, uint32_t *ReturnLens) {
-  if (!C || !ReturnLens) return R(kWrongVMWorkflow);
-  if (!C->shards.empty()) return wbm::return_lens(C, ReturnLens);
-  if (!C->calls_on && C->func < 0) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs / BatchSetCalls not called"));
-  if (C->calls_on && !C->calls_mirror()) return R(kRuntimeError);
-  for (uint32_t i = 0; i < C->n; i++)
-    ReturnLens[i] = !C->calls_on ? uint32_t(C->result_types.size())
-                    : C->call_func[i] < 0 ? 0u
-                    : uint32_t(C->prog.types[C->prog.funcs[C->call_func[i]].type].results.size());
-  return R(0);
-}
-
 WasmEdge_Result WasmEdge_BatchReset(WasmEdge_BatchContext *C, double *KernelSeconds) {
   if (!C) return R(kWrongVMWorkflow);
   if (!C->shards.empty()) return wbm::reset(C, KernelSeconds);
@@ -1022,16 +855,16 @@ WasmEdge_Result WasmEdge_BatchRun(WasmEdge_BatchContext *C, double *KernelSecond
   if (!C) return R(kWrongVMWorkflow);
   if (!C->shards.empty()) return wbm::run(C, KernelSeconds);
   DevScope dev(C);
-  if (C->func < 0 && !C->calls_on) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs not called"));
+  if (C->staged.func < 0 && !C->staged.calls_on) return R(C->fail(kWrongVMWorkflow, "BatchSetArgs not called"));
   if (C->restage)
     return R(C->fail(kWrongVMWorkflow, "BatchRun: the restored invocation's arguments are not staged "
                                        "(BatchSetArgs / BatchSetCalls first)"));
-  if (C->calls_on ? C->calls_import : C->prog.funcs[C->func].imported)
+  if (C->staged.calls_on ? C->staged.calls_import : C->prog.funcs[C->staged.func].imported)
     return R(C->fail(kRuntimeError, "exported function is a host import"));
   const bool measure = C->trial == 1 || C->trial == 3;
   double ks = 0;
   C->end_invocation();   // (a suspended invocation ends where the next one starts)
-  C->inv_pc = C->calls_on ? kCallsPc : C->prog.funcs[C->func].entry_pc;
+  C->inv_pc = C->staged.calls_on ? kCallsPc : C->prog.funcs[C->staged.func].entry_pc;
   uint8_t e = launch_exec(C, C->inv_pc, false, KernelSeconds || measure ? &ks : nullptr);
   if (e) return R(e);
   if (KernelSeconds) *KernelSeconds = ks;
@@ -1072,456 +905,6 @@ uint32_t WasmEdge_BatchGetSuspendedCount(const WasmEdge_BatchContext *C) {
   for (const WasmEdge_BatchContext *s : C->shards)
     if (s) n += WasmEdge_BatchGetSuspendedCount(s);
   return n;
-}
-
-WasmEdge_Result WasmEdge_BatchResults(WasmEdge_BatchContext *C, WasmEdge_Value *Returns,
-                                      const uint32_t ReturnLen, uint8_t *PerInstance,
-                                      uint64_t *InstrCounts) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty()) return wbm::results(C, Returns, ReturnLen, PerInstance, InstrCounts);
-  if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
-  if (C->calls_on && Returns && ReturnLen && !C->calls_mirror()) return R(kRuntimeError);
-  std::vector<uint8_t> st(C->n);
-  if (!C->hip_ok(hipMemcpy(st.data(), C->status.ptr, C->n, hipMemcpyDeviceToHost), "status"))
-    return R(kRuntimeError);
-  if (PerInstance) memcpy(PerInstance, st.data(), C->n);
-  if (InstrCounts &&
-      !C->hip_ok(hipMemcpy(InstrCounts, C->counts.ptr, size_t(C->n) * 8, hipMemcpyDeviceToHost), "counts"))
-    return R(kRuntimeError);
-  if (Returns && ReturnLen) {
-    uint32_t rc = C->result_cells;
-    std::vector<uint32_t> cells(size_t(C->n) * (rc ? rc : 1));
-    if (rc && !C->hip_ok(hipMemcpy(cells.data(), C->results.ptr, cells.size() * 4,
-                                   hipMemcpyDeviceToHost), "results"))
-      return R(kRuntimeError);
-    // (per-instance calls: each row carries its own function's result types, and an instance
-    // that sat the run out a row of zeroes -- the device wrote nothing there)
-    static const std::vector<uint8_t> none;
-    for (uint32_t i = 0; i < C->n; i++) {
-      const std::vector<uint8_t> &types = !C->calls_on ? C->result_types
-                                          : C->call_func[i] < 0 ? none
-                                          : C->prog.types[C->prog.funcs[C->call_func[i]].type].results;
-      if (C->calls_on)
-        for (uint32_t k = uint32_t(types.size()); k < ReturnLen; k++) Returns[size_t(i) * ReturnLen + k] = WasmEdge_Value{};
-      uint32_t at = 0;
-      for (uint32_t k = 0; k < types.size(); k++) {
-        uint8_t ty = types[k];
-        uint128_t v = 0;
-        for (uint32_t q = 0; q < cells_of_value(ty); q++)
-          v |= uint128_t(cells[size_t(i) * rc + at++]) << (32 * q);
-        if (k < ReturnLen) {
-          WasmEdge_Value &out = Returns[size_t(i) * ReturnLen + k];
-          out.Value = st[i] != 0 ? 0 : ty == wb::EXTERNREF ? C->xref_out(uint32_t(v)) : v;
-          out.Type = static_cast<enum WasmEdge_ValType>(ty);
-        }
-      }
-    }
-  }
-  return R(0);
-}
-
-// ---- device-resident arguments and results (args_io.hip; DESIGN.md "Device-resident
-// arguments and results") ----------------------------------------------------------------
-}  // extern "C"
-namespace {
-// Rows [0, n) of `row` bytes, `stride` bytes apart from Buf on, lie inside an allocation on
-// the context's device -- as far as this HIP runtime knows the allocation (hostcall.cpp
-// mem_io: one it does not know, a framework's with a runtime of its own, is the caller's word)
-bool device_rows_ok(WasmEdge_BatchContext *C, const void *Buf, uint64_t row, uint64_t stride, const char *what) {
-  if (!Buf || !row || !C->n) return true;
-  hipPointerAttribute_t at{};
-  void *base = nullptr;
-  size_t size = 0;
-  const bool known = hipPointerGetAttributes(&at, Buf) == hipSuccess && at.type != hipMemoryTypeUnregistered;
-  if (!known) {
-    (void)hipGetLastError();
-    return true;
-  }
-  if (at.type != hipMemoryTypeDevice || at.device != C->device ||
-      hipMemGetAddressRange(&base, &size, const_cast<void *>(Buf)) != hipSuccess) {
-    (void)hipGetLastError();
-    C->fail(kRuntimeError, std::string(what) + ": not a buffer on the context's device");
-    return false;
-  }
-  const uint64_t room = uint64_t(size) - uint64_t(static_cast<const uint8_t *>(Buf) - static_cast<uint8_t *>(base));
-  if (room < row || (C->n > 1 && stride > (room - row) / (C->n - 1))) {
-    C->fail(kRuntimeError, std::string(what) + ": the device buffer is smaller than NumInstances rows");
-    return false;
-  }
-  return true;
-}
-bool has_externref(const std::vector<uint8_t> &types) {
-  return std::find(types.begin(), types.end(), uint8_t(wb::EXTERNREF)) != types.end();
-}
-// the table on the device, uploaded when it differs from the one there (`host`)
-bool upload_map(WasmEdge_BatchContext *C, WasmEdge_BatchContext::DevBuf<uint32_t> &dev, std::vector<uint32_t> &host,
-                std::vector<uint32_t> &map) {
-  if (dev.ptr && host == map) return true;
-  host.clear();   // (nothing valid there until the copy is queued)
-  if (dev.n < map.size() && !dev.alloc(map.size())) {
-    (void)hipGetLastError();
-    C->fail(kRuntimeError, "device allocation failed");
-    return false;
-  }
-  host.swap(map);   // (the copy's source lives as long as the context)
-  return C->hip_ok(hipMemcpyAsync(dev.ptr, host.data(), host.size() * 4, hipMemcpyHostToDevice, C->stream),
-                   "signature table upload");
-}
-}  // namespace
-extern "C" {
-
-WasmEdge_Result WasmEdge_BatchSetArgsDevice(WasmEdge_BatchContext *C, const WasmEdge_String FuncName,
-                                            const enum WasmEdge_ValType *ParamTypes, const uint32_t ParamLen,
-                                            const uint64_t *Slots, const uint64_t Stride) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty())
-    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchSetArgs"));
-  DevScope dev(C);
-  std::string name(FuncName.Buf ? FuncName.Buf : "", FuncName.Length);
-  const int f = wb::find_export(C->prog, name);
-  if (f < 0) return R(C->fail(kFuncNotFound, "function '" + name + "' not found"));
-  const wb::FuncType &t = C->prog.types[C->prog.funcs[f].type];
-  // executor.cpp:88-100, on the type array: a device row carries no tags
-  if (ParamLen != t.params.size()) return R(C->fail(kFuncSigMismatch, "parameter count mismatch"));
-  if (ParamLen && !ParamTypes) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: null ParamTypes"));
-  for (uint32_t k = 0; k < ParamLen; k++)
-    if (uint8_t(ParamTypes[k]) != t.params[k]) return R(C->fail(kFuncSigMismatch, "parameter type mismatch"));
-  if (has_externref(t.params) || has_externref(t.results))
-    return R(C->fail(kRuntimeError, "BatchSetArgsDevice: externref values are interned on the host: use BatchSetArgs"));
-  // cell c of a row is word map[c] of the slot row
-  std::vector<uint32_t> map;
-  uint64_t need = 0;
-  for (uint8_t ty : t.params) {
-    for (uint32_t q = 0; q < cells_of_value(ty); q++) map.push_back(uint32_t(need * 2 + q));
-    need += ty == wb::V128 ? 2 : 1;
-  }
-  const uint32_t pc = uint32_t(map.size());
-  if (need && !Slots) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: null Slots"));
-  if (Stride < need) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Stride is smaller than a row"));
-  if (need && (uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Slots is not 8-byte aligned"));
-  if (need && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchSetArgsDevice: Stride out of range"));
-  if (!device_rows_ok(C, Slots, need * 8, Stride * 8, "BatchSetArgsDevice")) return R(kRuntimeError);
-  uint32_t rc = 0;
-  for (uint8_t ty : t.results) rc += cells_of_value(ty);
-  const size_t pn = size_t(C->n) * (pc ? pc : 1), rn = size_t(C->n) * (rc ? rc : 1);
-  if ((C->params.n != pn || !C->params.ptr) && !C->params.alloc(pn))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  if (!C->args_sum.ptr && !C->args_sum.alloc(1)) return R(C->fail(kRuntimeError, "device allocation failed"));
-  C->args_sum_h = 0;
-  if (pc) {
-    if (!upload_map(C, C->pack_map, C->pack_map_h, map)) return R(kRuntimeError);
-    ArgsPackParams p{};
-    p.slots = Slots;
-    p.word_of = C->pack_map.ptr;
-    p.params = C->params.ptr;
-    p.fp = C->args_sum.ptr;
-    p.stride = Stride;
-    p.n = C->n;
-    p.cells = pc;
-    if (!C->hip_ok(hipMemsetAsync(C->args_sum.ptr, 0, 8, C->stream), "fingerprint") ||
-        !C->hip_ok(wb_launch_args_pack(&p, C->stream), "args pack") ||
-        !C->hip_ok(hipMemcpyAsync(&C->args_sum_h, C->args_sum.ptr, 8, hipMemcpyDeviceToHost, C->stream), "fingerprint"))
-      return R(kRuntimeError);
-  }
-  if (!C->hip_ok(hipStreamSynchronize(C->stream), "args pack")) return R(kRuntimeError);
-  // the function and the cells' order-independent sum (args_io.h): equal for equal device
-  // arguments, not the value BatchSetArgs gives the same arguments
-  C->args_fp = args_fp_mix(~uint64_t(f), 0xA5A5A5A5u) + C->args_sum_h;
-  C->func = f;
-  C->param_cells = pc;
-  C->result_cells = rc;
-  C->result_types = t.results;
-  C->calls_on = false;   // (back to one function for every instance)
-  C->restage = false;
-  C->end_invocation();   // (new staging: a suspended invocation cannot continue)
-  return R(0);
-}
-
-WasmEdge_Result WasmEdge_BatchResultsDevice(WasmEdge_BatchContext *C, uint64_t *Slots, const uint32_t ReturnLen,
-                                            const uint64_t Stride, uint8_t *PerInstance, uint64_t *InstrCounts) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty())
-    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchResults"));
-  if (C->calls_on)
-    return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: per-instance calls have no device rows: use BatchResults"));
-  if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
-  DevScope dev(C);
-  // word w of the written part of a row is result cell map[w] (or zero)
-  std::vector<uint32_t> map;
-  uint32_t cell = 0;
-  for (uint32_t k = 0; Slots && k < ReturnLen && k < C->result_types.size(); k++) {
-    const uint8_t ty = C->result_types[k];
-    if (ty == wb::EXTERNREF)
-      return R(C->fail(kRuntimeError, "BatchResultsDevice: externref values are interned on the host: use BatchResults"));
-    const uint32_t nc = cells_of_value(ty);
-    for (uint32_t q = 0; q < nc; q++) map.push_back(cell++);
-    if (nc == 1) map.push_back(kArgsNoCell);
-  }
-  const uint64_t need = map.size() / 2;
-  if (Stride < need) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Stride is smaller than a row"));
-  if (need && (uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Slots is not 8-byte aligned"));
-  if (need && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: Stride out of range"));
-  if (InstrCounts && (uintptr_t(InstrCounts) & 7u))
-    return R(C->fail(kWrongVMWorkflow, "BatchResultsDevice: InstrCounts is not 8-byte aligned"));
-  if (!device_rows_ok(C, Slots, need * 8, Stride * 8, "BatchResultsDevice") ||
-      !device_rows_ok(C, PerInstance, 1, 1, "BatchResultsDevice") ||
-      !device_rows_ok(C, InstrCounts, 8, 8, "BatchResultsDevice"))
-    return R(kRuntimeError);
-  // (every launch and host-import round of the run has ended: launch_once waits for its
-  // kernel, a restore of a suspended invocation for its own)
-  if (need) {
-    const uint32_t words = uint32_t(map.size());
-    if (!upload_map(C, C->unpack_map, C->unpack_map_h, map)) return R(kRuntimeError);
-    ArgsUnpackParams p{};
-    p.results = C->results.ptr;
-    p.status = C->status.ptr;
-    p.cell_of = C->unpack_map.ptr;
-    p.slots = Slots;
-    p.stride = Stride;
-    p.n = C->n;
-    p.cells = C->result_cells;
-    p.words = words;
-    if (!C->hip_ok(wb_launch_args_unpack(&p, C->stream), "results unpack")) return R(kRuntimeError);
-  }
-  if (PerInstance && !C->hip_ok(hipMemcpyAsync(PerInstance, C->status.ptr, C->n, hipMemcpyDeviceToDevice, C->stream), "status"))
-    return R(kRuntimeError);
-  if (InstrCounts && !C->hip_ok(hipMemcpyAsync(InstrCounts, C->counts.ptr, size_t(C->n) * 8, hipMemcpyDeviceToDevice,
-                                               C->stream), "counts"))
-    return R(kRuntimeError);
-  if (!C->hip_ok(hipStreamSynchronize(C->stream), "results unpack")) return R(kRuntimeError);
-  return R(0);
-}
-
-// ---- device-resident per-instance calls (calls_io.hip; DESIGN.md "Device-resident
-// per-instance calls") -------------------------------------------------------------------
-}  // extern "C"
-namespace {
-template <typename T>
-void swap_bufs(WasmEdge_BatchContext::DevBuf<T> &a, WasmEdge_BatchContext::DevBuf<T> &b) {
-  std::swap(a.ptr, b.ptr);
-  std::swap(a.n, b.n);
-}
-template <typename T>
-bool sized(WasmEdge_BatchContext::DevBuf<T> &b, size_t count) {
-  return (b.ptr && b.n == count) || b.alloc(count);
-}
-}  // namespace
-extern "C" {
-
-// BatchSetCalls from a device FuncOf and device slot rows. The host resolves the NumFuncs
-// names into a table; one kernel turns FuncOf and the rows into the call table, the cells and
-// call_fn in the spare buffers and reduces the fingerprint, the lowest invalid FuncOf index and
-// the "an import is called" flag into 16 bytes, read back with the call's one synchronise. A
-// valid vector swaps the spare buffers in; an invalid one leaves the live staging as it was.
-WasmEdge_Result WasmEdge_BatchSetCallsDevice(WasmEdge_BatchContext *C, const WasmEdge_String *FuncNames,
-                                             const uint32_t NumFuncs, const enum WasmEdge_ValType *const *ParamTypes,
-                                             const uint32_t *ParamLens, const uint32_t *FuncOf,
-                                             const uint64_t *Slots, const uint64_t Stride) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty())
-    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchSetCalls"));
-  if (!FuncOf || (NumFuncs && !FuncNames))
-    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null FuncOf / FuncNames"));
-  if ((ParamTypes == nullptr) != (ParamLens == nullptr))
-    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: ParamTypes and ParamLens go together"));
-  DevScope dev(C);
-  const wb::Program &P = C->prog;
-  // the per-name table (calls_io.h), then the names' word_of maps
-  std::vector<uint32_t> tab(size_t(NumFuncs) * kCallsFnWords + 1, 0), maps;
-  uint64_t widest = 0;
-  uint32_t pc = 0, rc = 0, res_slots = 0;
-  for (uint32_t j = 0; j < NumFuncs; j++) {
-    uint32_t *row = &tab[size_t(j) * kCallsFnWords];
-    const std::string name(FuncNames[j].Buf ? FuncNames[j].Buf : "", FuncNames[j].Length);
-    const int f = wb::find_export(P, name);
-    row[kCallsFnEntry] = WB_CALL_SKIP | kFuncNotFound;
-    row[kCallsFnFunc] = 0xFFFFFFFFu;
-    if (f < 0) continue;
-    const wb::FuncInfo &F = P.funcs[f];
-    const wb::FuncType &t = P.types[F.type];
-    if (has_externref(t.params) || has_externref(t.results))
-      return R(C->fail(kRuntimeError, "BatchSetCallsDevice: '" + name + "' takes or returns an externref, which is "
-                                      "interned on the host: use BatchSetCalls"));
-    std::vector<uint32_t> map;
-    uint64_t need = 0;
-    for (uint8_t ty : t.params) {
-      for (uint32_t q = 0; q < cells_of_value(ty); q++) map.push_back(uint32_t(need * 2 + q));
-      need += ty == wb::V128 ? 2 : 1;
-    }
-    widest = std::max(widest, need);
-    // executor.cpp:88-100, on the type arrays: a device row carries no tags
-    bool ok = true;
-    if (ParamTypes) {
-      ok = ParamLens[j] == t.params.size();
-      if (ok && ParamLens[j] && !ParamTypes[j])
-        return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null ParamTypes row"));
-      for (uint32_t k = 0; ok && k < ParamLens[j]; k++) ok = uint8_t(ParamTypes[j][k]) == t.params[k];
-    }
-    if (!ok) {
-      row[kCallsFnEntry] = WB_CALL_SKIP | kFuncSigMismatch;
-      continue;
-    }
-    uint32_t frc = 0, fslots = 0;
-    for (uint8_t ty : t.results) {
-      frc += cells_of_value(ty);
-      fslots += ty == wb::V128 ? 2 : 1;
-    }
-    pc = std::max(pc, uint32_t(map.size()));
-    rc = std::max(rc, frc);
-    res_slots = std::max(res_slots, fslots);
-    row[kCallsFnEntry] = F.imported ? WB_CALL_SKIP : F.entry_pc;   // (an import: BatchRun refuses)
-    row[kCallsFnCells] = uint32_t(map.size());
-    row[kCallsFnFunc] = uint32_t(f);
-    row[kCallsFnImport] = F.imported ? 1u : 0u;
-    row[kCallsFnMap] = uint32_t(maps.size());   // (relative; the table's length is added below)
-    maps.insert(maps.end(), map.begin(), map.end());
-  }
-  for (uint32_t j = 0; j < NumFuncs; j++) tab[size_t(j) * kCallsFnWords + kCallsFnMap] += uint32_t(tab.size());
-  tab.insert(tab.end(), maps.begin(), maps.end());
-  if (widest && !Slots) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: null Slots"));
-  if (Stride < widest) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Stride is smaller than the widest row"));
-  if ((uintptr_t(Slots) & 7u)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Slots is not 8-byte aligned"));
-  if ((uintptr_t(FuncOf) & 3u)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: FuncOf is not 4-byte aligned"));
-  if (widest && Stride > (~0ull >> 4)) return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: Stride out of range"));
-  if (!device_rows_ok(C, FuncOf, 4, 4, "BatchSetCallsDevice") ||
-      !device_rows_ok(C, Slots, widest * 8, Stride * 8, "BatchSetCallsDevice"))
-    return R(kRuntimeError);
-  // the spare buffers the kernel writes; the result rows change size only on success
-  const uint32_t pcs = pc ? pc : 1;
-  const size_t pn = size_t(C->n) * pcs, rn = size_t(C->n) * (rc ? rc : 1);
-  WasmEdge_BatchContext::DevBuf<uint32_t> results;
-  if (!sized(C->params_spare, pn) || !sized(C->calls_spare, size_t(C->n) * 2) || !sized(C->call_fn_spare, C->n) ||
-      !sized(C->calls_sum, 1) || ((C->results.n != rn || !C->results.ptr) && !results.alloc(rn))) {
-    (void)hipGetLastError();
-    return R(C->fail(kRuntimeError, "device allocation failed"));
-  }
-  if (!upload_map(C, C->calls_tab, C->calls_tab_h, tab)) return R(kRuntimeError);
-  CallsPackParams p{};
-  p.func_of = FuncOf;
-  p.slots = Slots;
-  p.table = C->calls_tab.ptr;
-  p.calls = C->calls_spare.ptr;
-  p.params = C->params_spare.ptr;
-  p.call_fn = C->call_fn_spare.ptr;
-  p.sum = C->calls_sum.ptr;
-  p.stride = Stride;
-  p.n = C->n;
-  p.pc = pcs;
-  p.nfuncs = NumFuncs;
-  if (!C->hip_ok(hipMemsetAsync(C->calls_sum.ptr, 0, sizeof(CallsSummary), C->stream), "call summary") ||
-      !C->hip_ok(wb_launch_calls_pack(&p, C->stream), "calls pack") ||
-      !C->hip_ok(hipMemcpyAsync(&C->calls_sum_h, C->calls_sum.ptr, sizeof(CallsSummary), hipMemcpyDeviceToHost,
-                                C->stream), "call summary") ||
-      !C->hip_ok(hipStreamSynchronize(C->stream), "calls pack"))
-    return R(kRuntimeError);
-  if (C->calls_sum_h.bad)
-    return R(C->fail(kWrongVMWorkflow, "BatchSetCallsDevice: FuncOf[" + std::to_string(~C->calls_sum_h.bad) +
-                                       "] names no function"));
-  swap_bufs(C->params, C->params_spare);
-  swap_bufs(C->calls, C->calls_spare);
-  swap_bufs(C->call_fn, C->call_fn_spare);
-  if (results.ptr) swap_bufs(C->results, results);
-  // the vector's and the cells' order-independent sum: equal for equal device vectors, not
-  // the value BatchSetCalls gives the same vector
-  C->args_fp = args_fp_mix(~uint64_t(1), 0xC0C0C0C0u) + C->calls_sum_h.fp;
-  C->func = -1;
-  C->param_cells = pcs;
-  C->result_cells = rc;
-  C->result_types.clear();
-  C->call_host_ok = false;   // (call_func / call_status: fetched on first need, calls_mirror)
-  C->call_dev_ok = true;
-  C->calls_res_slots = res_slots;
-  C->calls_xref = false;
-  C->calls_import = C->calls_sum_h.imported != 0;
-  C->calls_on = true;
-  C->restage = false;
-  C->end_invocation();
-  return R(0);
-}
-
-WasmEdge_Result WasmEdge_BatchCallsResultsDevice(WasmEdge_BatchContext *C, uint64_t *Slots, const uint32_t Width,
-                                                 const uint64_t Stride, uint32_t *ReturnLens, uint8_t *PerInstance,
-                                                 uint64_t *InstrCounts) {
-  if (!C) return R(kWrongVMWorkflow);
-  if (!C->shards.empty())
-    return R(C->fail(kRuntimeError, "a device buffer cannot serve a multi-device context: use BatchResults"));
-  if (!C->calls_on)
-    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: no per-instance calls are staged: use BatchResultsDevice"));
-  if (!C->ran) return R(C->fail(kWrongVMWorkflow, "BatchRun not called"));
-  if (Slots && Stride < Width) return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Stride is smaller than Width"));
-  if (Slots && Width < C->calls_res_slots)
-    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Width is smaller than the widest result row (" +
-                                       std::to_string(C->calls_res_slots) + " slots)"));
-  if ((uintptr_t(Slots) & 7u) || (uintptr_t(InstrCounts) & 7u) || (uintptr_t(ReturnLens) & 3u))
-    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: a misaligned pointer"));
-  if (Slots && Width && Stride > (~0ull >> 4))
-    return R(C->fail(kWrongVMWorkflow, "BatchCallsResultsDevice: Stride out of range"));
-  if (Slots && C->calls_xref)
-    return R(C->fail(kRuntimeError, "BatchCallsResultsDevice: externref values are interned on the host: use BatchResults"));
-  DevScope dev(C);
-  const uint32_t width = Slots ? Width : 0;
-  if (!device_rows_ok(C, Slots, uint64_t(width) * 8, Stride * 8, "BatchCallsResultsDevice") ||
-      !device_rows_ok(C, ReturnLens, 4, 4, "BatchCallsResultsDevice") ||
-      !device_rows_ok(C, PerInstance, 1, 1, "BatchCallsResultsDevice") ||
-      !device_rows_ok(C, InstrCounts, 8, 8, "BatchCallsResultsDevice"))
-    return R(kRuntimeError);
-  // (every launch and host-import round of the run has ended: launch_once waits for its
-  // kernel, a restore of a suspended invocation for its own)
-  if (width || ReturnLens) {
-    // each instance's function on the device: there already after SetCallsDevice, uploaded
-    // after BatchSetCalls or a restore that rewrote call_func on the host
-    if (!C->call_dev_ok) {
-      if (!sized(C->call_fn, C->n)) {
-        (void)hipGetLastError();
-        return R(C->fail(kRuntimeError, "device allocation failed"));
-      }
-      if (!C->hip_ok(hipMemcpyAsync(C->call_fn.ptr, C->call_func.data(), size_t(C->n) * 4, hipMemcpyHostToDevice,
-                                    C->stream), "call vector upload"))
-        return R(kRuntimeError);
-      C->call_dev_ok = true;
-    }
-    // the module's result table (calls_io.h), built and uploaded once
-    if (C->res_tab_h.empty()) {
-      const wb::Program &P = C->prog;
-      std::vector<uint32_t> tab(P.funcs.size() * kCallsResWords, 0), maps;
-      for (size_t f = 0; f < P.funcs.size(); f++) {
-        const std::vector<uint8_t> &types = P.types[P.funcs[f].type].results;
-        uint32_t cell = 0;
-        tab[f * kCallsResWords + kCallsResLen] = uint32_t(types.size());
-        tab[f * kCallsResWords + kCallsResMap] = uint32_t(tab.size() + maps.size());
-        for (uint8_t ty : types) {
-          const uint32_t nc = cells_of_value(ty);
-          for (uint32_t q = 0; q < nc; q++) maps.push_back(cell++);
-          if (nc == 1) maps.push_back(kArgsNoCell);
-        }
-        tab[f * kCallsResWords + kCallsResSlots] = uint32_t(tab.size() + maps.size() - tab[f * kCallsResWords + kCallsResMap]) / 2;
-      }
-      tab.insert(tab.end(), maps.begin(), maps.end());
-      tab.push_back(0);   // (never empty)
-      if (!upload_map(C, C->res_tab, C->res_tab_h, tab)) return R(kRuntimeError);
-    }
-    CallsUnpackParams p{};
-    p.results = C->results.ptr;
-    p.status = C->status.ptr;
-    p.call_fn = C->call_fn.ptr;
-    p.table = C->res_tab.ptr;
-    p.slots = Slots;
-    p.lens = ReturnLens;
-    p.stride = Stride;
-    p.n = C->n;
-    p.cells = C->result_cells;
-    p.width = width;
-    if (!C->hip_ok(wb_launch_calls_unpack(&p, C->stream), "results unpack")) return R(kRuntimeError);
-  }
-  if (PerInstance && !C->hip_ok(hipMemcpyAsync(PerInstance, C->status.ptr, C->n, hipMemcpyDeviceToDevice, C->stream), "status"))
-    return R(kRuntimeError);
-  if (InstrCounts && !C->hip_ok(hipMemcpyAsync(InstrCounts, C->counts.ptr, size_t(C->n) * 8, hipMemcpyDeviceToDevice,
-                                               C->stream), "counts"))
-    return R(kRuntimeError);
-  if (!C->hip_ok(hipStreamSynchronize(C->stream), "results unpack")) return R(kRuntimeError);
-  return R(0);
 }
 
 WasmEdge_Result WasmEdge_BatchExecute(WasmEdge_BatchContext *C, const WasmEdge_String FuncName,
@@ -1865,13 +1248,11 @@ WasmEdge_Result WasmEdge_BatchGlobalGetValue(WasmEdge_BatchContext *C, const Was
   if (g < 0) return R(C->fail(kFuncNotFound, "global export not found"));
   if (Inst >= C->n) return R(C->fail(kRuntimeError, "instance index out of range"));
   const uint8_t t = P.global_types[g];
-  uint128_t v = 0;
-  for (uint32_t q = 0; q < wb::cells_of(t); q++) {
-    uint32_t w = 0;
-    if (!get_lane(C, C->lstate.ptr, C->ls_slots, LS_GLOBALS + P.global_cell[g] + q, Inst, &w))
+  uint32_t w[4] = {0, 0, 0, 0};
+  for (uint32_t q = 0; q < wb::cells_of(t); q++)
+    if (!get_lane(C, C->lstate.ptr, C->ls_slots, LS_GLOBALS + P.global_cell[g] + q, Inst, &w[q]))
       return R(kRuntimeError);
-    v |= uint128_t(w) << (32 * q);
-  }
+  uint128_t v = wb::from_cells(t, w);
   if ((t == wb::FUNCREF || t == wb::EXTERNREF) && uint32_t(v) == 0xFFFFFFFFu) v = 0xFFFFFFFFu;
   if (t == wb::EXTERNREF) v = C->xref_out(uint32_t(v));
   Value->Value = v;
@@ -1901,9 +1282,9 @@ WasmEdge_Result WasmEdge_BatchGlobalSetValue(WasmEdge_BatchContext *C, const Was
   bool full = false;
   const uint128_t x = t == wb::EXTERNREF ? uint128_t(C->xref_in(Value.Value, &full)) : Value.Value;
   if (full) return R(C->fail(kRuntimeError, "externref intern table full (2^31 - 1 values)"));
-  for (uint32_t q = 0; q < wb::cells_of(t); q++)
-    if (!put_lane(C, C->lstate.ptr, C->ls_slots, LS_GLOBALS + P.global_cell[g] + q, Inst,
-                  uint32_t(x >> (32 * q))))
+  uint32_t w[4];
+  for (uint32_t q = 0, nc = wb::to_cells(t, x, w); q < nc; q++)
+    if (!put_lane(C, C->lstate.ptr, C->ls_slots, LS_GLOBALS + P.global_cell[g] + q, Inst, w[q]))
       return R(kRuntimeError);
   return R(0);
 }

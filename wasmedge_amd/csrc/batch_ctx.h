@@ -1,9 +1,11 @@
 // batch_ctx.h -- the batch context shared by the C-ABI translation units
-// (batch_api.cpp: create/run/results; hostcall.cpp: the host-import service rounds;
-// wasi.cpp: the built-in WASI subset). Host-only; never included by device code.
+// (batch_api.cpp: create/run; staging.cpp: arguments and results; hostcall.cpp: the
+// host-import service rounds; wasi.cpp: the built-in WASI subset). Host-only; never included
+// by device code.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -18,6 +20,7 @@
 #include "kparams.h"
 #include "mem_layout.h"
 #include "calls_io.h"
+#include "sig_layout.h"
 #include "wasi_impl.h"
 
 namespace wbh {
@@ -52,6 +55,26 @@ struct DevBuf {
     if (v.empty()) return true;
     return hipMemcpyAsync(ptr, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice, s) == hipSuccess;
   }
+};
+
+// The host's description of what is staged for the next Run (staging.cpp): written whole by a
+// Set call, held whole by a snapshot of a suspended invocation (snapshot.cpp).
+struct Staging {
+  int func = -1;   // the function every instance runs; -1: none, or per-instance calls
+  uint32_t param_cells = 0, result_cells = 0;   // the row strides of params / results
+  std::vector<uint8_t> result_types;            // func's (empty with calls_on)
+  // per-instance calls (WasmEdge_BatchSetCalls): each instance's function (-1: it sits the run
+  // out, with call_status), whether a named export is a host import (BatchRun then fails as
+  // for a uniform one), the widest result row of the functions in slots, and whether one
+  // returns an externref
+  bool calls_on = false, calls_import = false;
+  std::vector<int32_t> call_func;
+  std::vector<uint8_t> call_status;
+  uint32_t calls_res_slots = 0;
+  bool calls_xref = false;
+  uint64_t args_fp = 1;   // fingerprint of the staged arguments (wave order, layout trial)
+  // the same function or call vector on the same arguments
+  bool same_run(const Staging &o) const { return args_fp == o.args_fp && func == o.func && calls_on == o.calls_on; }
 };
 
 }  // namespace wbh
@@ -128,7 +151,7 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> wave_ticks, wave_order;
   uint32_t order_pc = 0xFFFFFFFFu;   // entry pc of the launch the order was taken from
                                      // (kCallsPc: per-instance calls, their vector in the fp)
-  uint64_t order_fp = 0, args_fp = 1;   // its arguments' fingerprint; the staged arguments'
+  uint64_t order_fp = 0;             // its arguments' fingerprint (Staging::args_fp then)
   bool lpt = true;
   uint32_t sched = 1;             // KParams::sched (WB_SCHED=k; 0: min-pc scheduling only)
   DevBuf<uint32_t> loops;         // Program::loops (scheduler)
@@ -209,18 +232,12 @@ struct WasmEdge_BatchContext {
     return a ? reinterpret_cast<uint32_t *>(a) + size_t(word & 16383u) * 64 : nullptr;
   }
   uint32_t mlog = 0;              // log2(words per memory interleave granule), KParams::mlog
-  // current invocation
-  int func = -1;
-  uint32_t param_cells = 0, result_cells = 0;
-  std::vector<uint8_t> result_types;
-  // per-instance calls (WasmEdge_BatchSetCalls; a plain SetArgs clears calls_on): the device
-  // table (KParams::calls), each instance's function (-1: it sits the run out, with
-  // call_status) and whether a named export is a host import (BatchRun then fails as for a
-  // uniform one); param_cells / result_cells are the row strides
-  bool calls_on = false, calls_import = false;
-  DevBuf<uint32_t> calls;
-  std::vector<int32_t> call_func;
-  std::vector<uint8_t> call_status;
+  // staging (staging.cpp): what is staged, then its device-side companions
+  wbh::Staging staged;
+  // a restore reinstated a suspended invocation (snapshot.cpp) whose function or arguments the
+  // staged ones no longer match: BatchRun asks for SetArgs / SetCalls first (they clear it)
+  bool restage = false;
+  DevBuf<uint32_t> calls;   // the per-instance call table (KParams::calls)
   // device-resident arguments and results (WasmEdge_BatchSetArgsDevice / ResultsDevice,
   // args_io.h): the per-signature tables on the device with the host copies they were
   // uploaded from (a call with the same signature uploads nothing), and the device word the
@@ -230,13 +247,12 @@ struct WasmEdge_BatchContext {
   DevBuf<uint64_t> args_sum;
   uint64_t args_sum_h = 0;
   // device-resident per-instance calls (WasmEdge_BatchSetCallsDevice / CallsResultsDevice,
-  // calls_io.h). call_fn is call_func on the device; one flag per side says which copy is
-  // current (calls_mirror / CallsResultsDevice bring the other up to date on first need).
+  // calls_io.h). call_fn is staged.call_func on the device; one flag per side says which copy
+  // is current (calls_mirror / CallsResultsDevice bring the other up to date on first need).
   // The pack kernel writes the spare buffers, swapped in when the call succeeds, so a refused
   // FuncOf leaves the live staging runnable. calls_tab: the per-name table of the last
   // SetCallsDevice, res_tab: the per-function result table of the module (built once), each
-  // with the host copy it was uploaded from. calls_res_slots / calls_xref: the widest result
-  // row of the staging's functions in slots, and whether one returns an externref.
+  // with the host copy it was uploaded from (sig_layout.h builds both).
   DevBuf<int32_t> call_fn, call_fn_spare;
   DevBuf<uint32_t> calls_spare, params_spare;
   bool call_host_ok = true, call_dev_ok = false;
@@ -244,8 +260,6 @@ struct WasmEdge_BatchContext {
   std::vector<uint32_t> calls_tab_h, res_tab_h;
   DevBuf<CallsSummary> calls_sum;
   CallsSummary calls_sum_h{};
-  uint32_t calls_res_slots = 0;
-  bool calls_xref = false;
   // call_func / call_status after a SetCallsDevice, which read back only the summary: fetched
   // from call_fn and the call table's entries (the staging call synchronised its stream)
   bool calls_mirror() {
@@ -253,29 +267,26 @@ struct WasmEdge_BatchContext {
     // (the whole [n][2] table in one copy: a strided copy of the entries alone took 6 ms at
     // 65,536 instances)
     std::vector<uint32_t> tab(size_t(n) * 2);
-    call_func.assign(n, -1);
-    call_status.assign(n, 0);
-    if (!hip_ok(hipMemcpy(call_func.data(), call_fn.ptr, size_t(n) * 4, hipMemcpyDeviceToHost), "call vector") ||
+    staged.call_func.assign(n, -1);
+    staged.call_status.assign(n, 0);
+    if (!hip_ok(hipMemcpy(staged.call_func.data(), call_fn.ptr, size_t(n) * 4, hipMemcpyDeviceToHost), "call vector") ||
         !hip_ok(hipMemcpy(tab.data(), calls.ptr, tab.size() * 4, hipMemcpyDeviceToHost), "call vector"))
       return false;
-    for (uint32_t i = 0; i < n; i++) call_status[i] = tab[2 * size_t(i)] >= WB_CALL_SKIP ? uint8_t(tab[2 * size_t(i)]) : 0;
+    for (uint32_t i = 0; i < n; i++) staged.call_status[i] = tab[2 * size_t(i)] >= WB_CALL_SKIP ? uint8_t(tab[2 * size_t(i)]) : 0;
     call_host_ok = true;
     return true;
   }
-  // calls_res_slots / calls_xref from call_func (the host copy is current)
+  // staged.calls_res_slots / calls_xref from call_func (the host copy is current)
   void calls_shape() {
-    calls_res_slots = 0;
-    calls_xref = false;
+    staged.calls_res_slots = 0;
+    staged.calls_xref = false;
     std::vector<uint8_t> seen(prog.funcs.size(), 0);
-    for (int32_t f : call_func) {
+    for (int32_t f : staged.call_func) {
       if (f < 0 || seen[f]) continue;
       seen[f] = 1;
-      uint32_t slots = 0;
-      for (uint8_t ty : prog.types[prog.funcs[f].type].results) {
-        slots += ty == wb::V128 ? 2 : 1;
-        calls_xref |= ty == wb::EXTERNREF;
-      }
-      if (slots > calls_res_slots) calls_res_slots = slots;
+      const wb::SigLayout L = wb::layout_of(prog.types[prog.funcs[f].type]);
+      staged.calls_res_slots = std::max(staged.calls_res_slots, L.result_slots);
+      staged.calls_xref |= L.result_xref;
     }
   }
   // device-resident spans (WasmEdge_BatchWriteMemoriesSpansDevice / ReadMemoriesSpansDevice,
@@ -286,8 +297,8 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> span_lane, span_wave, span_sum;
   bool span_flip = false;
   uint32_t spans_tiled = 0;
-  // resumable runs (conf.Resumable; DESIGN.md "Resumable runs"): the invocation BatchResume
-  // continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
+  // current invocation: with resumable runs (conf.Resumable; DESIGN.md "Resumable runs") the
+  // one BatchResume continues -- live from a completed BatchRun until Reset / SetArgs / SetCalls / the next
   // Run / SnapshotRestore --, its entry pc, the cumulative step limit of the call in
   // progress (BatchResume's; a Run takes conf.MaxSteps), the device counter the kernel adds
   // suspended lanes to (KParams::suspended) and its value after the last Run / Resume
@@ -298,9 +309,6 @@ struct WasmEdge_BatchContext {
   DevBuf<uint32_t> susp_ctr;
   uint32_t suspended = 0;
   void end_invocation() { inv_live = false; suspended = 0; }
-  // a restore reinstated a suspended invocation (snapshot.cpp) whose function or arguments the
-  // staged ones no longer match: BatchRun asks for SetArgs / SetCalls first (they clear it)
-  bool restage = false;
   bool ran = false;        // a Run completed since the last Reset (results are valid)
   bool mem_fresh = true;    // memory never initialised: the next Reset writes every page
   // A Reset that skipped its host sync left init kernels queued on `stream` (non-blocking,
@@ -445,6 +453,19 @@ struct WaveView {
   bool flush();
 };
 
+// Rows [0, n) of `row` bytes, `stride` bytes apart from Buf on, lie inside an allocation on the
+// context's device -- as far as this HIP runtime knows the allocation: one it does not know (a
+// framework that brings a HIP runtime of its own allocates there) is the caller's word.
+// false: last_error = the text of the half that failed (staging.cpp)
+bool device_rows_ok(WasmEdge_BatchContext *C, const void *Buf, uint64_t row, uint64_t stride, const char *not_device,
+                    const char *too_small);
+// ... with the texts of the entry point `what`
+inline bool device_rows_ok(WasmEdge_BatchContext *C, const void *Buf, uint64_t row, uint64_t stride, const char *what) {
+  if (!Buf || !row) return true;   // (nothing to check: no message is built)
+  const std::string w(what);
+  return device_rows_ok(C, Buf, row, stride, (w + ": not a buffer on the context's device").c_str(),
+                        (w + ": the device buffer is smaller than NumInstances rows").c_str());
+}
 uint8_t mem_rw(WasmEdge_BatchContext *C, uint32_t Inst, uint32_t Off, uint32_t Len,
                uint8_t *Dst, const uint8_t *Src);
 // bulk transfer (hostcall.cpp, mem_io.hip): rows of the [n][Stride] buffer Buf (`device`: a

@@ -5,18 +5,11 @@
 #include <stdint.h>
 
 #include "args_io.h"
+#include "kparams.h"
 
-// The per-function table of a staging, one row of kCallsFnWords words per name of FuncNames,
-// then the names' word_of maps back to back (the meaning of ArgsPackParams::word_of: the
-// 32-bit word of the slot row each parameter cell takes).
-constexpr uint32_t kCallsFnWords = 5;
-constexpr uint32_t kCallsFnEntry = 0;    // calls[2i]: entry pc, or WB_CALL_SKIP | status (an import: WB_CALL_SKIP)
-constexpr uint32_t kCallsFnCells = 1;    // calls[2i + 1]: parameter cells (0 unless the function runs)
-constexpr uint32_t kCallsFnFunc = 2;     // module function index, 0xFFFFFFFF (-1): not found / mismatch
-constexpr uint32_t kCallsFnImport = 3;   // 1: the export is a host import
-constexpr uint32_t kCallsFnMap = 4;      // offset of its word_of map, in words from the table's start
+static_assert(kCallSkip == WB_CALL_SKIP, "sig_layout.h names kparams.h's word");
 
-constexpr uint32_t kCallsNoCall = 0xFFFFFFFFu;   // WASMEDGE_BATCH_NO_CALL
+// (sig_layout.h: the per-name table and the per-module result table, kCallsFn* / kCallsRes*)
 
 // What the pack kernel reduces into, zero at the launch; the host reads it back in one copy.
 struct CallsSummary {
@@ -39,14 +32,6 @@ struct CallsPackParams {
   uint64_t stride;           // slots per row
   uint32_t n, pc, nfuncs;    // pc > 0
 };
-
-// The per-module result table, one row of kCallsResWords words per module function, then the
-// functions' cell_of maps (two words per result slot: the result cell of the slot's low word,
-// then of its high word or kArgsNoCell).
-constexpr uint32_t kCallsResWords = 3;
-constexpr uint32_t kCallsResLen = 0;     // result values (BatchGetReturnLens)
-constexpr uint32_t kCallsResSlots = 1;   // result slots
-constexpr uint32_t kCallsResMap = 2;     // offset of its cell_of map
 
 // KParams::results -> slot rows of `width` slots: the function's result slots, then zeroes; a
 // row whose status is not 0 or whose call_fn is negative is all zeroes. lens[i] (when not

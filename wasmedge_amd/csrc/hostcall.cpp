@@ -193,26 +193,9 @@ uint8_t mem_io(WasmEdge_BatchContext *C, const uint32_t *Offsets, uint32_t Offse
   if (!C->settle() || !pool_upload(C)) return kRuntimeError;
   const uint32_t n = C->n;
   if (n == 0) return 0;
-  if (device && Len) {
-    // An allocation this HIP runtime knows must be device memory of this context's device
-    // and hold NumInstances rows. One it does not know (hipMemoryTypeUnregistered: a
-    // framework that brings a HIP runtime of its own allocates there) is the caller's word.
-    hipPointerAttribute_t at{};
-    void *base = nullptr;
-    size_t size = 0;
-    const bool known = hipPointerGetAttributes(&at, Buf) == hipSuccess && at.type != hipMemoryTypeUnregistered;
-    if (!known) (void)hipGetLastError();
-    if (known && (at.type != hipMemoryTypeDevice || at.device != C->device ||
-                  hipMemGetAddressRange(&base, &size, Buf) != hipSuccess)) {
-      (void)hipGetLastError();
-      return C->fail(kRuntimeError, "memories: not a buffer on the context's device");
-    }
-    if (known) {
-      const uint64_t room = uint64_t(size) - uint64_t(Buf - static_cast<uint8_t *>(base));
-      if (room < Len || (n > 1 && Stride > (room - Len) / (n - 1)))
-        return C->fail(kRuntimeError, "memories: the device buffer is smaller than NumInstances rows");
-    }
-  }
+  if (device && !device_rows_ok(C, Buf, Len, Stride, "memories: not a buffer on the context's device",
+                                "memories: the device buffer is smaller than NumInstances rows"))
+    return kRuntimeError;
   DevBuf<uint32_t> d_off, d_len;
   DevBuf<uint8_t> d_st, stage;
   if (!d_st.alloc(n) || (Offsets && !d_off.alloc(n)) || (Lens && !d_len.alloc(n))) {
@@ -900,8 +883,8 @@ int64_t service_host_calls(WasmEdge_BatchContext *C) {
         rets.assign(t.results.size(), WasmEdge_Value{});
         uint32_t at = 0;
         for (size_t q = 0; q < t.params.size(); q++) {
-          uint128_t v = 0;
-          for (uint32_t c = 0; c < wb::cells_of(t.params[q]); c++) v |= uint128_t(cells[at++]) << (32 * c);
+          const uint128_t v = wb::from_cells(t.params[q], &cells[at]);
+          at += wb::cells_of(t.params[q]);
           args[q].Value = t.params[q] == wb::EXTERNREF ? C->xref_out(uint32_t(v)) : v;
           args[q].Type = static_cast<enum WasmEdge_ValType>(t.params[q]);
         }
@@ -918,7 +901,7 @@ int64_t service_host_calls(WasmEdge_BatchContext *C) {
         bool full = false;
         for (size_t q = 0; q < t.results.size(); q++) {
           const uint128_t v = t.results[q] == wb::EXTERNREF ? uint128_t(C->xref_in(rets[q].Value, &full)) : rets[q].Value;
-          for (uint32_t c = 0; c < wb::cells_of(t.results[q]); c++) cells[at++] = uint32_t(v >> (32 * c));
+          at += wb::to_cells(t.results[q], v, &cells[at]);
         }
         if (full) {   // (the intern table is full: the host function's result cannot pass)
           st[i] = 0x8D;   // HostFuncFailed

@@ -55,13 +55,8 @@ struct WasmEdge_BatchSnapshot {
   DevBuf<uint8_t> status;
   std::vector<uint8_t> susp_h;    // [n] 1: suspended (parked with WB_SUSPENDED in hcall)
   uint32_t suspended = 0;         // their number
-  int func = -1;
-  uint32_t param_cells = 0, result_cells = 0, inv_pc = 0;
-  std::vector<uint8_t> result_types;
-  bool calls_on = false, calls_import = false;
-  std::vector<int32_t> call_func;
-  std::vector<uint8_t> call_status;
-  uint64_t args_fp = 0;           // the staging it ran under (Run after a restore: restage)
+  wbh::Staging staged;            // the staging it ran under (call_func / call_status current)
+  uint32_t inv_pc = 0;
   // the last restore's plan and its device copy (kept here so that an untimed restore leaves
   // nothing of its own to free while its kernels run)
   mutable wbs::RestorePlan plan;
@@ -155,7 +150,7 @@ bool capture_invocation(Ctx *C, Snap *S) {
       !C->hip_ok(hipStreamSynchronize(C->stream), "snapshot") ||
       !C->hip_ok(hipMemcpy(hc.data(), C->hcall.ptr, size_t(C->n) * 4, hipMemcpyDeviceToHost), "snapshot"))
     return false;
-  if (C->calls_on && !C->calls_mirror()) return false;   // (a device-staged vector: fetched now)
+  if (C->staged.calls_on && !C->calls_mirror()) return false;   // (a device-staged vector: fetched now)
   S->susp_h.assign(C->n, 0);
   S->suspended = 0;
   for (uint32_t i = 0; i < C->n; i++)
@@ -163,16 +158,8 @@ bool capture_invocation(Ctx *C, Snap *S) {
       S->susp_h[i] = 1;
       S->suspended++;
     }
-  S->func = C->func;
-  S->param_cells = C->param_cells;
-  S->result_cells = C->result_cells;
-  S->result_types = C->result_types;
+  S->staged = C->staged;
   S->inv_pc = C->inv_pc;
-  S->calls_on = C->calls_on;
-  S->calls_import = C->calls_import;
-  S->call_func = C->call_func;
-  S->call_status = C->call_status;
-  S->args_fp = C->args_fp;
   S->has_inv = true;
   return true;
 }
@@ -275,32 +262,6 @@ void delete_one(Snap *S) {
                   hipSetDevice(S->device) == hipSuccess;
   delete S;   // (its device buffers)
   if (sw) (void)hipSetDevice(cur);
-}
-
-// NumInstances words from Buf on lie inside an allocation on the context's device, as far as
-// this HIP runtime knows the allocation (hostcall.cpp mem_io: one it does not know, a
-// framework's with a runtime of its own, is the caller's word)
-bool device_map_ok(Ctx *C, const uint32_t *Buf) {
-  DevScope dev(C);
-  hipPointerAttribute_t at{};
-  void *base = nullptr;
-  size_t size = 0;
-  if (hipPointerGetAttributes(&at, Buf) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
-    (void)hipGetLastError();
-    return true;
-  }
-  if (at.type != hipMemoryTypeDevice || at.device != C->device ||
-      hipMemGetAddressRange(&base, &size, const_cast<uint32_t *>(Buf)) != hipSuccess) {
-    (void)hipGetLastError();
-    C->fail(kRuntimeError, "restore: the map is not a buffer on the context's device");
-    return false;
-  }
-  const uint64_t room = uint64_t(size) - uint64_t(reinterpret_cast<const uint8_t *>(Buf) - static_cast<uint8_t *>(base));
-  if (room < uint64_t(C->n) * 4) {
-    C->fail(kRuntimeError, "restore: the device map is smaller than NumInstances words");
-    return false;
-  }
-  return true;
 }
 
 uint8_t rows_launch(Ctx *C, uint32_t *dst, const uint32_t *src, const uint32_t *src_of, uint32_t words_d,
@@ -424,7 +385,7 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, const uint32_t
     if (need > C->gs_depth && !grow_stack(C, S->gs_depth))
       return C->fail(kRuntimeError, "restore: the call stack cannot grow back to the depth of the capture "
                                     "(device memory, CallStackMaxBytes)");
-    const size_t rn = size_t(C->n) * (S->result_cells ? S->result_cells : 1);
+    const size_t rn = size_t(C->n) * (S->staged.result_cells ? S->staged.result_cells : 1);
     if ((SrcOf && !S->gs_plan_d.ptr && !S->gs_plan_d.alloc(S->gs_plan.size())) ||
         ((C->results.n != rn || !C->results.ptr) && !C->results.alloc(rn))) {
       (void)hipGetLastError();
@@ -523,7 +484,7 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, const uint32_t
     q.results_s = S->results.ptr;
     q.src_of = src_of;
     q.n = C->n;
-    q.result_cells = S->result_cells;
+    q.result_cells = S->staged.result_cells;
     if (!e && !C->hip_ok(wb_launch_snap_inst(&q, C->stream), "restore")) e = kRuntimeError;
   }
   if (e) return e;
@@ -546,22 +507,19 @@ uint8_t restore_one(Ctx *C, const Snap *S, const uint32_t *SrcOf, const uint32_t
   if (S->has_inv) {
     // the invocation's descriptor, the per-instance fields through SrcOf; BatchResume
     // continues it and BatchResults reads the rows as they stood (it does not settle: wait)
-    C->restage = SrcOf || C->args_fp != S->args_fp || C->func != S->func || C->calls_on != S->calls_on;
-    C->func = S->func;
-    C->param_cells = S->param_cells;
-    C->result_cells = S->result_cells;
-    C->result_types = S->result_types;
-    C->calls_on = S->calls_on;
-    C->calls_import = S->calls_import;
-    C->call_func = S->call_func;
-    C->call_status = S->call_status;
+    // (the arguments on the device stay the staged ones, so their fingerprint stays too: a
+    // Run needs them staged again unless they are what the invocation ran on)
+    const uint64_t fp = C->staged.args_fp;
+    C->restage = SrcOf || !C->staged.same_run(S->staged);
+    C->staged = S->staged;
+    C->staged.args_fp = fp;
     C->suspended = 0;
     for (uint32_t i = 0; i < C->n; i++) {
       const uint32_t s = SrcOf ? SrcOf[i] : i;
       C->suspended += S->susp_h[s];
-      if (S->calls_on && SrcOf) {
-        C->call_func[i] = S->call_func[s];
-        C->call_status[i] = S->call_status[s];
+      if (S->staged.calls_on && SrcOf) {
+        C->staged.call_func[i] = S->staged.call_func[s];
+        C->staged.call_status[i] = S->staged.call_status[s];
       }
     }
     // (calls_io: the host copy is the current one, CallsResultsDevice uploads it on first need)
@@ -737,7 +695,12 @@ WasmEdge_Result WasmEdge_BatchSnapshotRestoreSelectedDevice(WasmEdge_BatchContex
   if (S->ctx != C) return R(C->fail(kWrongVMWorkflow, "restore: the snapshot was taken from another context"));
   if (!C->shards.empty())
     return R(C->fail(kRuntimeError, "restore: a device map on a multi-device context (use the host entry)"));
-  if (!device_map_ok(C, SrcOfDevice)) return R(kRuntimeError);
+  {   // NumInstances words there, as far as this HIP runtime knows the allocation
+    DevScope dev(C);
+    if (!device_rows_ok(C, SrcOfDevice, 4, 4, "restore: the map is not a buffer on the context's device",
+                        "restore: the device map is smaller than NumInstances words"))
+      return R(kRuntimeError);
+  }
   return R(restore_one(C, S, nullptr, SrcOfDevice, true, NumRestored, KernelSeconds));
 }
 
